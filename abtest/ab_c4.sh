@@ -5,7 +5,7 @@
 set -uo pipefail
 mkdir -p gpurun_out/ab
 export TMPDIR=/tmp
-ARGS="--no-config2 --no-alg3-chunked --cpu-seconds 0 --steps ${STEPS:-3} --warmup 1 ${EXTRA:-}"
+ARGS="--full --no-config2 --no-alg3-chunked --cpu-seconds 0 --steps ${STEPS:-3} --warmup 1 ${EXTRA:-}"
 for v in $VARIANTS; do
   SPG_LIB=$PWD/spmm_amd/lib/libv_$v.so timeout -k 10 240 python bench.py $ARGS > gpurun_out/ab/$v.json 2> gpurun_out/ab/$v.err || { echo "$v bench rc=$?"; exit 1; }
   python3 -c "import json,sys; d=json.load(open('gpurun_out/ab/$v.json')); print('$v', d['value'], d['ms_per_step'], d['phases_ms_per_step'])"

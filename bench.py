@@ -23,17 +23,24 @@ Workloads (``--config``; ``auto`` = 4 at every N):
   reduction.  value = sum_r 2 P_r / max-over-ranks time.
 * ``2`` (BASELINE configs[1]): random 16384 x 16384, density 1e-3, fp64, A then B from one
   ``default_rng(42)`` stream via scipy.sparse.random (nnz(C) = 4,366,124, P = 4,402,284), ALG1
-  single pass.  Reported as the ``config2`` key of the N=1 line.
+  single pass.  Reported as the ``config2`` key of the N=1 line (``--full``).
 * ``5``: N = 262144, density 1e-3, fp64, ALG2, STRONG scaling over the ranks (north_star's
   8-GPU configuration): rank r owns the rows [r0, r1) cut on the product-count prefix, B
-  (826 MB) broadcast inside every step.  At N > 1 it is also reported as the ``config5`` key
-  of the line (``--config5-n 0`` skips it).
+  (826 MB) broadcast inside every step.  At N > 1 ``--full`` also reports it as the
+  ``config5`` key of the line (``--config5-n 0`` skips it).
 
 ``python3 bench.py --gpus N`` (N > 1) without a launcher spawns N worker processes itself
 (before anything touches the GPU) with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, exactly
 as ``torch.distributed.run`` would; under a launcher (WORLD_SIZE set) it is one rank.
 
-Also reported: ``roofline`` for the numeric-phase kernel (compulsory bytes of the product,
+A plain run (``--gpus N --steps K --warmup W``) sets up, runs W untimed and K timed steps
+and prints the line: ``value``, ``ms_per_step``, ``peak_hbm_bytes`` and ``config`` of the
+workload above.  ``--dump-outputs DIR`` also writes the C of the last timed step as
+DIR/<name>.npy (``dump_outputs``; the inputs are seeded, so the same arguments give the same
+arrays from run to run and from build to build).  Everything below takes runs of its own and
+is measured only with ``--full``: the ``config2`` / ``alg3_chunked`` / ``config3_fp32`` keys
+at N=1; ``b_broadcast_ms``, ``b_values_pipeline`` and the ``config5`` key at N > 1;
+``phases_ms_per_step``; ``roofline`` for the numeric-phase kernel (compulsory bytes of the product,
 SURVEY 8d, / the phase's device time from HIP events on the library's stream, per launch),
 ``cpu_baseline`` = scipy's ``A @ B`` -- the reference's CPU comparator
 (SpGEMM_vs_SpMV/profiler.py:408) -- timed in forked children with their RSS growth, on
@@ -96,6 +103,12 @@ def parse(argv=None):
                     help="N>1: size of the strong-scaled config5 key (0 skips it)")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="PMC traffic summary written by profiles/pmc_to_json.py")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: phases and roofline (extra steps), the "
+                         "CPU baseline, the config2 / alg3_chunked / config3_fp32 keys (N=1), the broadcast "
+                         "timings, b_values_pipeline and the config5 key (N>1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the C of the last timed step as DIR/<name>.npy (a fixed sample when C is large)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: tests only (gloo, --multiply-hook as the per-rank multiply)")
     ap.add_argument("--multiply-hook", default=None,
@@ -304,6 +317,41 @@ def timed(ctx, step, steps, warmup):
     return time.perf_counter() - t0, C
 
 
+DUMP_ENTRIES = 1 << 20   # entries of one array --dump-outputs keeps (3 arrays + positions: 32 MB)
+
+
+def dump_outputs(ctx, out_dir, C):
+    """``--dump-outputs DIR``: the CSR arrays of the C the last timed step returned, as
+    DIR/indptr.npy, DIR/indices.npy and DIR/data.npy (``_rank<r>`` appended at N > 1).  indptr
+    and indices in float64 (exact: both stay below 2^53), data in C's own precision.  An array
+    of more than DUMP_ENTRIES entries is written at DUMP_ENTRIES positions drawn from
+    ``default_rng(0)`` (sorted, repeats allowed; indices and data share theirs) and the
+    positions go to DIR/indptr_positions.npy / DIR/entry_positions.npy: the same positions in
+    every run, so two builds given the same arguments are compared entry for entry."""
+    torch = ctx.torch
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if ctx.world == 1 else f"_rank{ctx.rank}"
+    rng = np.random.default_rng(0)
+
+    def positions(n):
+        return None if n <= DUMP_ENTRIES else np.sort(rng.integers(0, n, size=DUMP_ENTRIES))
+
+    def write(name, x, pos, npdt):
+        if pos is not None:
+            x = x.index_select(0, torch.from_numpy(pos).to(x.device))
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), x.cpu().numpy().astype(npdt))
+
+    pos = positions(C.indptr.numel())
+    write("indptr", C.indptr, pos, np.float64)
+    if pos is not None:
+        np.save(os.path.join(out_dir, f"indptr_positions{tag}.npy"), pos.astype(np.float64))
+    pos = positions(C.indices.numel())
+    write("indices", C.indices, pos, np.float64)
+    write("data", C.data, pos, np.float32 if C.data.dtype == torch.float32 else np.float64)
+    if pos is not None:
+        np.save(os.path.join(out_dir, f"entry_positions{tag}.npy"), pos.astype(np.float64))
+
+
 def phase_times(ctx, step, reps):
     """Per-phase device times of `reps` extra steps (HIP events on the library's stream,
     which is torch's current stream).  {} on CPU."""
@@ -401,7 +449,8 @@ def run_config4(ctx, args, cfg, tdt, vb, hook):
         P = int(distributed.product_prefix(A, Bw.indptr)[-1])
         nnzB = Bw.nnz
         del Bw
-        bcast_ms = broadcast_ms(ctx, B)
+        if args.full:
+            bcast_ms = broadcast_ms(ctx, B)
 
         def step():
             C, _ = distributed.rowblock_step(A, B, 0, ctx.dev, alg=alg, chunk_fraction=cf, multiply=hook,
@@ -416,6 +465,8 @@ def run_config4(ctx, args, cfg, tdt, vb, hook):
     elapsed, C = timed(ctx, step, steps, warmup)
     nnzC, ib_c = C.nnz, C.indptr.element_size()
     peak = last_peak(ctx)
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, C)
     del C
     if ctx.gpu:
         ctx.torch.cuda.empty_cache()
@@ -423,16 +474,17 @@ def run_config4(ctx, args, cfg, tdt, vb, hook):
     P_all, nnz_all = ctx.reduce([float(P), float(nnzC)], "sum")
     (peak_max,) = ctx.reduce([float(peak)], "max")
     ms = elapsed / steps * 1e3
-    reps = 2
-    ph = phase_times(ctx, step, reps)
-    bid, sid = lib_ids(ctx)
-    key = f"c4_n{n}_d{dens:g}_{args.dtype}_alg{alg}_w1"   # per-rank work = the N=1 product
-    traffic, tb = traffic_for(args.pmc, key, bid, sid) if ctx.gpu else (None, None)
     kname, nch = tile_kernel(ctx, A, B, alg, cf)
-    rf = roofline(ph, reps, kname, compulsory_bytes(A.shape[0], n, A.nnz, nnzB, nnzC, vb, ib_c), ms, traffic, tb,
-                  step_frac=(w == 1))
+    reps, ph, rf = 2, {}, None
+    if args.full:   # the phases and the roofline take steps of their own
+        ph = phase_times(ctx, step, reps)
+        bid, sid = lib_ids(ctx)
+        key = f"c4_n{n}_d{dens:g}_{args.dtype}_alg{alg}_w1"   # per-rank work = the N=1 product
+        traffic, tb = traffic_for(args.pmc, key, bid, sid) if ctx.gpu else (None, None)
+        rf = roofline(ph, reps, kname, compulsory_bytes(A.shape[0], n, A.nnz, nnzB, nnzC, vb, ib_c), ms, traffic,
+                      tb, step_frac=(w == 1))
     cpu = None
-    if r == 0 and w == 1 and args.cpu_seconds > 0 and ctx.gpu:
+    if args.full and r == 0 and w == 1 and args.cpu_seconds > 0 and ctx.gpu:
         A_h, B_h = A.get(), B.get()
         sample = np.sort(np.random.default_rng(0).choice(n, size=min(n, 1024), replace=False))
         cpu = cpu_baseline(A_h, B_h, sample, args.cpu_seconds)
@@ -456,7 +508,7 @@ def run_config4(ctx, args, cfg, tdt, vb, hook):
         "peak_hbm_bytes": int(peak_max), "roofline": rf,
         "phases_ms_per_step": {k: round(v[0] / reps, 5) for k, v in ph.items() if v[1]},
         "b_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 3),
-        "b_values_pipeline": None if w == 1 else pipeline_report(ctx, args, A, B, alg, cf, hook, ms),
+        "b_values_pipeline": pipeline_report(ctx, args, A, B, alg, cf, hook, ms) if (w > 1 and args.full) else None,
         "cpu_baseline": cpu,
     }
     del A, B
@@ -563,9 +615,10 @@ def last_peak(ctx):
     return cusparse.last_stats.peak_bytes
 
 
-def run_config5(ctx, args, cfg, n, tdt, vb, hook, steps, warmup):
+def run_config5(ctx, args, cfg, n, tdt, vb, hook, steps, warmup, dump=None):
     """Config 5 strong-scaled: the rows of one n x n A cut on the product prefix over the
-    ranks (each rank draws only its own block), B broadcast inside every step."""
+    ranks (each rank draws only its own block), B broadcast inside every step.  `dump`: the
+    --dump-outputs directory when this is the line's workload."""
     from spmm_amd import cusparse, distributed
     dens, alg, cf = cfg["density"], cfg["alg"], args.chunk_fraction
     w, r = ctx.world, ctx.rank
@@ -580,7 +633,7 @@ def run_config5(ctx, args, cfg, n, tdt, vb, hook, steps, warmup):
         del Bw
         if ctx.gpu:
             ctx.torch.cuda.empty_cache()
-        bcast_ms = broadcast_ms(ctx, B)
+        bcast_ms = broadcast_ms(ctx, B) if args.full else None
 
         def step():
             C, _ = distributed.rowblock_step(A, B, 0, ctx.dev, alg=alg, chunk_fraction=cf, multiply=hook,
@@ -596,6 +649,8 @@ def run_config5(ctx, args, cfg, n, tdt, vb, hook, steps, warmup):
     elapsed, C = timed(ctx, step, steps, warmup)
     nnzC, ib_c = C.nnz, C.indptr.element_size()
     peak = last_peak(ctx)
+    if dump:
+        dump_outputs(ctx, dump, C)
     del C
     if ctx.gpu:
         ctx.torch.cuda.empty_cache()
@@ -603,16 +658,17 @@ def run_config5(ctx, args, cfg, n, tdt, vb, hook, steps, warmup):
     P_all, nnz_all = ctx.reduce([float(P), float(nnzC)], "sum")
     (peak_max,) = ctx.reduce([float(peak)], "max")
     ms = elapsed / steps * 1e3
-    reps = 1
-    ph = phase_times(ctx, step, reps)
     kname, nch = tile_kernel(ctx, A, B, alg, cf)
-    rf = roofline(ph, reps, kname, compulsory_bytes(A.shape[0], n, A.nnz, nnzB, nnzC, vb, ib_c),
-                  ms, None, None, step_frac=False)
+    reps, ph, rf = 1, {}, None
+    if args.full:   # the phases and the roofline take a step of their own
+        ph = phase_times(ctx, step, reps)
+        rf = roofline(ph, reps, kname, compulsory_bytes(A.shape[0], n, A.nnz, nnzB, nnzC, vb, ib_c),
+                      ms, None, None, step_frac=False)
     out = {"gflops": round(2.0 * P_all * steps / elapsed / 1e9, 3), "ms_per_step": round(ms, 5),
            "steps": steps, "warmup": warmup, "scaling": "strong", "N": n, "density": dens, "alg": alg,
            "num_products": int(P_all), "nnzC": int(nnz_all), "rows_rank0": list(rows), "n_chunks": nch,
            "peak_hbm_bytes_max_rank": int(peak_max), "b_broadcast_ms": None if bcast_ms is None else round(bcast_ms, 3),
-           "b_values_pipeline": None if w == 1 else pipeline_report(ctx, args, A, B, alg, cf, hook, ms),
+           "b_values_pipeline": pipeline_report(ctx, args, A, B, alg, cf, hook, ms) if (w > 1 and args.full) else None,
            "roofline_rank0": rf, "phases_ms_per_step": {k: round(v[0] / reps, 5) for k, v in ph.items() if v[1]},
            "workload": (f"{cfg['name']}: random CSR {n}x{n} density={dens:g} {args.dtype}, ALG{alg}; "
                         f"{w} row blocks cut on the product prefix (each rank draws its own block), "
@@ -717,34 +773,38 @@ def run_config3_fp32(ctx, args, n=8192, dens=0.1, steps=10, warmup=2):
     return out
 
 
-def run_config2(ctx, args, cfg, npdt, vb, with_cpu):
-    """Config 2 (ALG1, N=16384) on one GPU: GFLOPS, its k_row roofline and the other ALGs."""
+def run_config2(ctx, args, cfg, npdt, vb, with_cpu, steps=None, warmup=None, dump=None):
+    """Config 2 (ALG1, N=16384) on one GPU: GFLOPS and, with --full, its k_row roofline and
+    the other ALGs.  `steps` / `warmup` / `dump`: --steps, --warmup and the --dump-outputs
+    directory when this is the line's workload (the config2 key keeps the config's own)."""
     from spmm_amd import _lib, cusparse, gen
     from spmm_amd.sparse import csr_matrix
     n, dens, alg, cf = cfg["n"], cfg["density"], cfg["alg"], args.chunk_fraction
     A_h, B_h = gen.scipy_pair(n, dens, seed=args.seed, dtype=npdt)
     A, B = csr_matrix(A_h, device=ctx.dev), csr_matrix(B_h, device=ctx.dev)
     P = cusparse.num_products(A, B)
-    steps, warmup = cfg["steps"], cfg["warmup"]
+    steps, warmup = pick(steps, cfg["steps"]), pick(warmup, cfg["warmup"])
 
     def step():
         return cusparse.spgemm(A, B, alg=alg, chunk_fraction=cf)
     elapsed, C = timed(ctx, step, steps, warmup)
     nnzC, ib_c = C.nnz, C.indptr.element_size()
     peak = cusparse.last_stats.peak_bytes
+    if dump:
+        dump_outputs(ctx, dump, C)
     del C
     ms = elapsed / steps * 1e3
-    other = {}
-    for a2 in (2, 3):
-        t, _ = timed(ctx, lambda: cusparse.spgemm(A, B, alg=a2, chunk_fraction=cf), max(5, steps // 2), 3)
-        dt = t / max(5, steps // 2)
-        other[f"alg{a2}"] = {"gflops": round(2.0 * P / dt / 1e9, 3), "ms_per_step": round(dt * 1e3, 5),
-                             "peak_hbm_bytes": int(cusparse.last_stats.peak_bytes)}
-    reps = 10
-    ph = phase_times(ctx, step, reps)
-    key = f"c2_n{n}_d{dens:g}_{args.dtype}_alg{alg}_w1"
-    traffic, tb = traffic_for(args.pmc, key, _lib.build_id(), _lib.source_id())
-    rf = roofline(ph, reps, "k_row", compulsory_bytes(n, n, A.nnz, B.nnz, nnzC, vb, ib_c), ms, traffic, tb)
+    other, reps, ph, rf = {}, 10, {}, None
+    if args.full:   # the other ALGs, the phases and the roofline take steps of their own
+        for a2 in (2, 3):
+            t, _ = timed(ctx, lambda: cusparse.spgemm(A, B, alg=a2, chunk_fraction=cf), max(5, steps // 2), 3)
+            dt = t / max(5, steps // 2)
+            other[f"alg{a2}"] = {"gflops": round(2.0 * P / dt / 1e9, 3), "ms_per_step": round(dt * 1e3, 5),
+                                 "peak_hbm_bytes": int(cusparse.last_stats.peak_bytes)}
+        ph = phase_times(ctx, step, reps)
+        key = f"c2_n{n}_d{dens:g}_{args.dtype}_alg{alg}_w1"
+        traffic, tb = traffic_for(args.pmc, key, _lib.build_id(), _lib.source_id())
+        rf = roofline(ph, reps, "k_row", compulsory_bytes(n, n, A.nnz, B.nnz, nnzC, vb, ib_c), ms, traffic, tb)
     out = {"gflops": round(2.0 * P * steps / elapsed / 1e9, 3), "ms_per_step": round(ms, 5),
            "steps": steps, "warmup": warmup, "N": n, "density": dens, "alg": alg, "nnzC": int(nnzC),
            "num_products": int(P), "peak_hbm_bytes": int(peak), "roofline": rf,
@@ -752,7 +812,7 @@ def run_config2(ctx, args, cfg, npdt, vb, with_cpu):
            "other_algs": other,
            "workload": (f"{cfg['name']}: random CSR {n}x{n} density={dens:g} {args.dtype} "
                         "(scipy.sparse.random, default_rng(42); A then B), ALG1 single-pass numeric")}
-    if with_cpu and args.cpu_seconds > 0:
+    if args.full and with_cpu and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(A_h, B_h, None, args.cpu_seconds)
     return out
 
@@ -779,25 +839,27 @@ def main(argv=None):
     if name == "4":
         res = run_config4(ctx, args, CONFIGS["4"], tdt, vb, hook)
         line.update(res)
-        if ctx.world == 1 and ctx.gpu and not args.no_config2:
+        if args.full and ctx.world == 1 and ctx.gpu and not args.no_config2:
             line["config2"] = run_config2(ctx, args, CONFIGS["2"], npdt, vb, with_cpu=False)
-        if ctx.world == 1 and ctx.gpu and not args.no_alg3_chunked:
+        if args.full and ctx.world == 1 and ctx.gpu and not args.no_alg3_chunked:
             line["alg3_chunked"] = run_alg3_chunked(ctx, args, tdt)
-        if ctx.world == 1 and ctx.gpu and not args.no_config2:
+        if args.full and ctx.world == 1 and ctx.gpu and not args.no_config2:
             line["config3_fp32"] = run_config3_fp32(ctx, args)
-        if ctx.world > 1 and args.config5_n > 0:
+        if args.full and ctx.world > 1 and args.config5_n > 0:
             line["config5"] = run_config5(ctx, args, CONFIGS["5"], args.config5_n, tdt, vb, hook,
                                           steps=3, warmup=1)
     elif name == "5":
         cfg = CONFIGS["5"]
         res = run_config5(ctx, args, cfg, pick(args.n, cfg["n"]), tdt, vb, hook,
-                          pick(args.steps, cfg["steps"]), pick(args.warmup, cfg["warmup"]))
+                          pick(args.steps, cfg["steps"]), pick(args.warmup, cfg["warmup"]),
+                          dump=args.dump_outputs)
         line.update({"value": res.pop("gflops"), "steps": res.pop("steps"), "warmup": res.pop("warmup"),
                      "ms_per_step": res.pop("ms_per_step"), "scaling": res.pop("scaling"),
                      "config": res, "peak_hbm_bytes": res.pop("peak_hbm_bytes_max_rank"),
                      "roofline": res.pop("roofline_rank0")})
     else:   # config 2 as the line (one GPU)
-        res = run_config2(ctx, args, CONFIGS["2"], npdt, vb, with_cpu=ctx.rank == 0)
+        res = run_config2(ctx, args, CONFIGS["2"], npdt, vb, with_cpu=ctx.rank == 0,
+                          steps=args.steps, warmup=args.warmup, dump=args.dump_outputs)
         line.update({"value": res.pop("gflops"), "steps": res.pop("steps"), "warmup": res.pop("warmup"),
                      "ms_per_step": res.pop("ms_per_step"), "scaling": "weak",
                      "peak_hbm_bytes": res.pop("peak_hbm_bytes"), "roofline": res.pop("roofline"),

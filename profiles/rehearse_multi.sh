@@ -6,7 +6,7 @@
 # parity.  Results in gpurun_out/ (committed as profiles/r03_rehearse_*.json).
 set -euo pipefail
 export SPG_DIST_BACKEND=gloo
-timeout -k 10 500 python3 bench.py --gpus 2 --steps 2 --warmup 1 --cpu-seconds 0 --config5-n 131072 \
+timeout -k 10 500 python3 bench.py --gpus 2 --full --steps 2 --warmup 1 --cpu-seconds 0 --config5-n 131072 \
     > gpurun_out/rehearse_bench.json 2> gpurun_out/rehearse_bench.err
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
     --master-port 29532 harness/multi_gpu/spgemm_rowblock.py --steps 1 --warmup 1 --check 32 \

@@ -63,7 +63,7 @@ def test_bench_spawns_ranks_without_launcher(tmp_path, world):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(bench.ROOT, "bench.py"), "--gpus", str(world), "--device", "cpu",
            "--multiply-hook", "tests.bench_hooks:oracle_multiply", "--n", str(n), "--config5-n", str(n5),
-           "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"]
+           "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--full"]
     r = subprocess.run(cmd, env=env, cwd=bench.ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -103,6 +103,66 @@ def test_bench_spawns_ranks_without_launcher(tmp_path, world):
     assert line["config5"]["num_products"] == oracle.num_products(A5, B5)
     r0, r1 = line["config5"]["rows_rank0"]
     assert r0 == 0 and 0 < r1 < n5
+
+
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path, monkeypatch):
+    """Without --full the line is the headline alone: no config5 key, no broadcast or pipeline
+    timings, no phases; --steps sets the timed steps.  --dump-outputs writes each rank's last C
+    (float64 / the data's own precision), equal to the slab the multiply hook returned; an array
+    longer than DUMP_ENTRIES is written at seeded positions that do not change from run to run."""
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    import torch
+
+    n, world = 600, 2
+    slab, out = str(tmp_path / "slab"), tmp_path / "dump"
+    env = dict(os.environ, SPG_BENCH_HOOK_DUMP=slab, PYTHONPATH=bench.ROOT)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(bench.ROOT, "bench.py"), "--gpus", str(world), "--device", "cpu",
+           "--multiply-hook", "tests.bench_hooks:oracle_multiply", "--n", str(n),
+           "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, cwd=bench.ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in line, k
+    assert "config5" not in line and "config2" not in line and "alg3_chunked" not in line
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["phases_ms_per_step"] == {}
+    assert line["b_broadcast_ms"] is None and line["b_values_pipeline"] is None
+    for k in range(world):
+        q = np.load(f"{slab}.n{n}.rank{k}.npz")
+        p, j, x = (np.load(out / f"{name}_rank{k}.npy") for name in ("indptr", "indices", "data"))
+        assert p.dtype == np.float64 and j.dtype == np.float64 and x.dtype == np.float64
+        assert np.array_equal(p, q["p"]) and np.array_equal(j, q["j"])
+        assert np.array_equal(x.view(np.uint64), q["x"].view(np.uint64))
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+
+    # the sampled form, in process: same positions on every call, values taken at them
+    from types import SimpleNamespace
+    OneRank = SimpleNamespace(world=1, rank=0, torch=torch)
+    C = SimpleNamespace(indptr=torch.arange(5, dtype=torch.int64), indices=torch.arange(40, dtype=torch.int32) * 3,
+                        data=torch.arange(40, dtype=torch.float32) / 7)
+
+    monkeypatch.setattr(bench, "DUMP_ENTRIES", 16)
+    got = []
+    for d in ("a", "b"):
+        bench.dump_outputs(OneRank, str(tmp_path / d), C)
+        got.append({f.name: np.load(f) for f in (tmp_path / d).iterdir()})
+    assert sorted(got[0]) == ["data.npy", "entry_positions.npy", "indices.npy", "indptr.npy"]
+    assert all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+    pos = got[0]["entry_positions.npy"].astype(np.int64)
+    assert len(pos) == 16 and np.all(np.diff(pos) >= 0) and pos.min() >= 0 and pos.max() < 40
+    assert np.array_equal(got[0]["indptr.npy"], np.arange(5, dtype=np.float64))
+    assert np.array_equal(got[0]["indices.npy"], (pos * 3).astype(np.float64))
+    assert got[0]["data.npy"].dtype == np.float32
+    assert np.array_equal(got[0]["data.npy"], C.data.numpy()[pos])
 
 
 def test_pick_keeps_explicit_zero():
