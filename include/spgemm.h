@@ -186,6 +186,35 @@ spg_status_t spg_numeric(spg_handle_t handle, spg_plan_t plan, const void *alpha
 spg_status_t spg_spmv(spg_handle_t handle, const spg_csr_t *A, const void *x, const void *alpha,
                       const void *beta, void *y);
 
+/* Dense matrix view of caller-owned device memory (cusparseCreateDnMat; DnMatDescriptor.create,
+ * cupy-src/cupyx/cusparse.py:1357-1370).  Element (i, j) sits at values[i * ld + j] for
+ * SPG_ORDER_ROW and at values[i + j * ld] for SPG_ORDER_COL; the numbers are cusparseOrder_t's. */
+typedef enum { SPG_ORDER_COL = 1, SPG_ORDER_ROW = 2 } spg_order_t;
+typedef struct {
+    int64_t rows, cols, ld; /* ld: elements between consecutive rows (ROW) or columns (COL) */
+    void *values;
+    spg_order_t order;
+    spg_dtype_t value_type;
+} spg_dense_t;
+
+/* Sparse matrix x dense matrix: C = alpha * A.B + beta * C (A CSR m x k, canonical; B dense
+ * k x n; C dense m x n; all of A's value type; alpha/beta host values).  Each C(i,c) is summed
+ * in A's entry order from 0, products and sums separately rounded, so the result equals
+ * scipy's csr_matvecs (A @ B) bit for bit -- spg_spmv's rule per column of B -- then
+ * v = alpha == 1 ? sum : alpha * sum and, only when beta != 0, v += beta * C: with beta == 0
+ * C is not read, so a NaN already in C does not reach the result.  B and C must have the same
+ * order (a mixed pair: SPG_STATUS_NOT_SUPPORTED); row-major operands whose base pointers and
+ * ld * sizeof(value) are multiples of 16 bytes take 16-byte accesses.  SPG_STATUS_INVALID_VALUE
+ * for B->rows != A->cols, a C that is not A->rows x B->cols, a value type other than A's, an
+ * ld below the minor extent (cols for ROW, rows for COL), NULL alpha, beta or a needed
+ * pointer.  m == 0 or n == 0 succeeds without a launch; an A with nnz == 0 still applies
+ * beta.  C overlapping B is undefined.  Stream-ordered; does not wait; no workspace.  Timed
+ * under SPG_PHASE_SPMV.  (cusparseSpMM as called by cupyx.cusparse.spmm,
+ * cupy-src/cupyx/cusparse.py:1494-1511; the dense half of others/spmm/spMM.py and
+ * others/spmm/diff_matrix_size.py.  Added within 0.2.0: a caller detects it by symbol lookup.) */
+spg_status_t spg_spmm(spg_handle_t handle, const spg_csr_t *A, const spg_dense_t *B,
+                      const void *alpha, const void *beta, spg_dense_t *C);
+
 /* ALG1 single pass: after spg_symbolic, C's column indices and values may already sit
  * compact in the workspace (nnzC entries at *indices / *values; NULL otherwise).  A
  * caller may hand exactly these pointers to spg_numeric as C->indices / C->values: the
@@ -312,7 +341,7 @@ typedef enum {
     SPG_PHASE_VALIDATE = 5,   /* k_validate                                         */
     SPG_PHASE_SPILL = 6,      /* k_symbolic / k_numeric over the rows the short-row */
                               /* kernel handed on (list mode)                        */
-    SPG_PHASE_SPMV = 7,       /* k_spmv                                             */
+    SPG_PHASE_SPMV = 7,       /* k_spmv / k_spmm                                    */
     SPG_PHASE_LAYOUT = 8,     /* the tile path's B re-layout: once per plan          */
                               /* (k_tile_index, k_bt_count, k_bj16, k_bt_pack) and   */
                               /* per tile group (k_bt_fill, spg_numeric_tiles)        */

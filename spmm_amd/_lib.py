@@ -28,6 +28,7 @@ SPG_R_64F = 1
 SPG_C_32F = 4
 SPG_C_64F = 5
 SPG_ALG_DEFAULT, SPG_ALG1, SPG_ALG2, SPG_ALG3 = 0, 1, 2, 3
+SPG_ORDER_COL, SPG_ORDER_ROW = 1, 2
 
 STATUS_NAMES = {
     0: "SPG_STATUS_SUCCESS", 1: "SPG_STATUS_NOT_INITIALIZED", 2: "SPG_STATUS_ALLOC_FAILED",
@@ -46,7 +47,7 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_numeric", "spg_peak_bytes", "spg_validate_csr", "spg_plan_destroy",
            "spg_set_timing", "spg_get_timing", "spg_result_in_workspace", "spg_spmv",
            "spg_spgemm_ws", "spg_plan_info", "spg_tile_value_offsets", "spg_tile_values",
-           "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join")
+           "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm")
 
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
@@ -58,6 +59,12 @@ class SpgCsr(ctypes.Structure):
                 ("indptr", ctypes.c_void_p), ("indices", ctypes.c_void_p),
                 ("values", ctypes.c_void_p), ("indptr_type", ctypes.c_int),
                 ("value_type", ctypes.c_int)]
+
+
+class SpgDense(ctypes.Structure):
+    """spg_dense_t"""
+    _fields_ = [("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("ld", ctypes.c_int64),
+                ("values", ctypes.c_void_p), ("order", ctypes.c_int), ("value_type", ctypes.c_int)]
 
 
 class SpgPlanInfo(ctypes.Structure):
@@ -100,6 +107,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         vp, i64, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t
         csrp = ctypes.POINTER(SpgCsr)
+        dnp = ctypes.POINTER(SpgDense)
         proto = {
             "spg_version": (ctypes.c_int, []),
             "spg_build_info": (ctypes.c_char_p, []),
@@ -113,6 +121,7 @@ def load():
             "spg_num_products": (ctypes.c_int, [vp, vp, ctypes.POINTER(i64)]),
             "spg_result_in_workspace": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]),
             "spg_spmv": (ctypes.c_int, [vp, csrp, vp, vp, vp, vp]),
+            "spg_spmm": (ctypes.c_int, [vp, csrp, dnp, vp, vp, dnp]),
             "spg_symbolic": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(i64)]),
             "spg_numeric": (ctypes.c_int, [vp, vp, vp, csrp]),
             "spg_peak_bytes": (ctypes.c_int, [vp, ctypes.POINTER(sz)]),

@@ -22,6 +22,7 @@
 #include "spgemm_tile_dn.hpp"
 #include "spgemm_spmv.hpp"
 #include "spgemm_row.hpp"
+#include "spgemm_spmm.hpp"
 
 using namespace spg;
 
@@ -1446,6 +1447,69 @@ __global__ __launch_bounds__(256) void k_cols16_join(int64_t rows, const IP* __r
     }
 }
 
+// ----------------------------------------------------------------------------- SpMM
+namespace {
+
+spg_status_t check_dense(const spg_dense_t* D) {
+    if (!D || D->rows < 0 || D->cols < 0) return SPG_STATUS_INVALID_VALUE;
+    if (D->order != SPG_ORDER_ROW && D->order != SPG_ORDER_COL) return SPG_STATUS_INVALID_VALUE;
+    if (D->ld < (D->order == SPG_ORDER_ROW ? D->cols : D->rows)) return SPG_STATUS_INVALID_VALUE;
+    if (D->rows > 0 && D->cols > 0 && !D->values) return SPG_STATUS_INVALID_VALUE;
+    return SPG_STATUS_SUCCESS;
+}
+
+// blocks of a kernel that strides over `tasks` wave tasks (the dispatch packet's work-item
+// count is 32-bit: see tile_grid)
+inline unsigned spmm_grid(int64_t tasks) {
+    const int64_t cap = ((int64_t)1 << 31) / ((int64_t)SPMM_WPB * WAVE);
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(tasks, SPMM_WPB), cap));
+}
+
+template <typename T, typename IP, int V>
+void spmm_row_launch(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& B, T al, T be, const spg_dense_t& C) {
+    const int64_t m = A.rows, n = B.cols;
+    const int64_t lanes = (n + V - 1) / V;   // lanes one row of C needs
+    const dim3 block(SPMM_WPB * WAVE);
+    if (lanes <= WAVE / 2) {                 // narrow B: 64 >> lgs rows per wave
+        int lgs = 0;
+        while ((1 << lgs) < lanes) ++lgs;
+        const int rpw = WAVE >> lgs;
+        hipLaunchKernelGGL((k_spmm_row_packed<T, IP, V>), dim3(spmm_grid(grid_for(m, rpw))), block, 0, h->stream, m,
+                           n, lgs, (const IP*)A.indptr, (const int32_t*)A.indices, (const T*)A.values,
+                           (const T*)B.values, B.ld, al, be, (T*)C.values, C.ld);
+    } else {
+        const int64_t strips = grid_for(n, WAVE * V);
+        hipLaunchKernelGGL((k_spmm_row<T, IP, V>), dim3(spmm_grid(m * strips)), block, 0, h->stream, m, n, strips,
+                           (const IP*)A.indptr, (const int32_t*)A.indices, (const T*)A.values,
+                           (const T*)B.values, B.ld, al, be, (T*)C.values, C.ld);
+    }
+}
+
+template <typename T, typename IP>
+spg_status_t spmm_launch(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& B, T al, T be,
+                         const spg_dense_t& C) {
+    PhaseTimer pt(h, SPG_PHASE_SPMV);
+    if (B.order == SPG_ORDER_ROW) {
+        constexpr int VMAX = SpmmGeom<T>::VMAX;
+        // 16-byte accesses need every row of B and C to start on a 16-byte boundary
+        const bool wide = VMAX > 1 && ((uintptr_t)B.values | (uintptr_t)C.values |
+                                       (uintptr_t)(B.ld * (int64_t)sizeof(T)) |
+                                       (uintptr_t)(C.ld * (int64_t)sizeof(T))) % 16 == 0;
+        if (wide) spmm_row_launch<T, IP, VMAX>(h, A, B, al, be, C);
+        else spmm_row_launch<T, IP, 1>(h, A, B, al, be, C);
+    } else {
+        const int64_t cstrips = grid_for(B.cols, SpmmColGeom<T>::NC);
+        hipLaunchKernelGGL((k_spmm_col<T, IP>), dim3(spmm_grid(row_groups(A.rows) * cstrips)),
+                           dim3(SPMM_WPB * WAVE), 0, h->stream, A.rows, B.cols, cstrips, (const IP*)A.indptr,
+                           (const int32_t*)A.indices, (const T*)A.values, (const T*)B.values, B.ld, al, be,
+                           (T*)C.values, C.ld);
+    }
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+}  // namespace
+
 extern "C" {
 
 int spg_version(void) { return SPG_VERSION_MAJOR * 10000 + SPG_VERSION_MINOR * 100 + SPG_VERSION_PATCH; }
@@ -2007,6 +2071,29 @@ spg_status_t spg_spmv(spg_handle_t h, const spg_csr_t* A, const void* x, const v
                                (const T*)x, al, be, (T*)y);
         SPG_LAUNCHED(h);
         return SPG_STATUS_SUCCESS;
+    });
+}
+
+spg_status_t spg_spmm(spg_handle_t h, const spg_csr_t* A, const spg_dense_t* B, const void* alpha,
+                      const void* beta, spg_dense_t* C) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    spg_status_t st = check_csr(A);
+    if (st) return st;
+    if (!alpha || !beta) return SPG_STATUS_INVALID_VALUE;
+    if ((st = check_dense(B)) || (st = check_dense(C))) return st;
+    if (B->value_type != A->value_type || C->value_type != A->value_type) return SPG_STATUS_INVALID_VALUE;
+    if (B->rows != A->cols || C->rows != A->rows || C->cols != B->cols) return SPG_STATUS_INVALID_VALUE;
+    if (B->order != C->order) return SPG_STATUS_NOT_SUPPORTED;
+    if (A->rows == 0 || B->cols == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    const bool i64 = A->indptr_type == SPG_INDEX_64I;
+    return dispatch_value(A->value_type, [&](auto tag) {
+        using T = decltype(tag);
+        T al, be;
+        std::memcpy(&al, alpha, sizeof(T));
+        std::memcpy(&be, beta, sizeof(T));
+        return i64 ? spmm_launch<T, int64_t>(h, *A, *B, al, be, *C) : spmm_launch<T, int32_t>(h, *A, *B, al, be, *C);
     });
 }
 

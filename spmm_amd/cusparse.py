@@ -58,7 +58,7 @@ def check_availability(name: str) -> bool:
     """True when the named routine can run here (a gfx950 device and the built library).
     Memoized like the reference's ``@_util.memoize()`` check (cusparse.py:169-186)."""
     global _available
-    if name not in ("spgemm", "spmv", "validate_csr"):
+    if name not in ("spgemm", "spmv", "spmm", "validate_csr"):
         raise ValueError(f"No available version information specified for {name}")
     if _available is None:
         try:
@@ -441,6 +441,104 @@ def spmv(a, x, y=None, alpha=1, beta=0, transa=False):
     return y
 
 
+def _dense_layout(t: torch.Tensor, prefer=None):
+    """(order, ld) of a 2-D tensor the engine can address in place, or None: unit stride
+    along columns is SPG_ORDER_ROW with ld = stride(0), unit stride along rows is
+    SPG_ORDER_COL with ld = stride(1).  An extent of 1 leaves its stride free, so such a
+    tensor may read as either order: `prefer` picks (row-major otherwise)."""
+    r, c = t.shape
+    s0, s1 = t.stride()
+    row = col = None
+    if (c <= 1 or s1 == 1) and (r <= 1 or s0 >= c):
+        row = (_lib.SPG_ORDER_ROW, max(s0 if r > 1 else c, 1))
+    if (r <= 1 or s0 == 1) and (c <= 1 or s1 >= r):
+        col = (_lib.SPG_ORDER_COL, max(s1 if c > 1 else r, 1))
+    if prefer == _lib.SPG_ORDER_COL and col is not None:
+        return col
+    return row or col
+
+
+def _dense_view(t: torch.Tensor, order: int, ld: int) -> _lib.SpgDense:
+    return _lib.SpgDense(t.shape[0], t.shape[1], ld, t.data_ptr() if t.numel() else 0, order, _VT[t.dtype])
+
+
+def _in_order(t: torch.Tensor, order: int) -> torch.Tensor:
+    """A copy of t with unit stride along columns (ROW) or rows (COL)."""
+    return t.contiguous() if order == _lib.SPG_ORDER_ROW else t.t().contiguous().t()
+
+
+def spmm(a, b, c=None, alpha=1, beta=0, transa=False, transb=False):
+    """C = alpha * op(A) op(B) + beta * C -- the drop-in for ``cupyx.cusparse.spmm``
+    (modify_src/cupy-src/cupyx/cusparse.py:1440-1513), on ``spg_spmm``.
+
+    A is csr_matrix, csc_matrix or coo_matrix (CSC goes through its transpose as the
+    reference does, COO through CSR).  b, c are 2-D tensors (or numpy arrays, uploaded) in
+    row-major or column-major layout, read from their strides; ``transb`` is a view and moves
+    no data.  The reference takes F-contiguous arrays only; both orders run here, and the
+    result has b's order (c's when c is given).  With CSR A, alpha = 1 and beta = 0 the result
+    equals scipy's ``A @ B`` bit for bit.
+    """
+    from .sparse import coo_matrix, csc_matrix
+    if not check_availability("spmm"):
+        raise RuntimeError("spmm is not available.")
+    if isinstance(a, csc_matrix):
+        a = a.T
+        transa = not transa
+    if not isinstance(a, (csr_matrix, coo_matrix)):
+        raise TypeError("unsupported type (actual: {})".format(type(a)))
+    if isinstance(a, coo_matrix):
+        a = a.tocsr()
+    if not isinstance(b, torch.Tensor):
+        b = torch.from_numpy(np.asarray(b))
+    assert a.ndim == b.ndim == 2
+    if transb:
+        b = b.t()
+    a_shape = a.shape if not transa else a.shape[::-1]
+    if a_shape[1] != b.shape[0]:
+        raise ValueError("dimension mismatch")
+    if transa:
+        a = a.transpose_csr()
+    assert a.has_canonical_format
+    dev = a.device
+    m, n = a_shape[0], b.shape[1]
+    dt = np.promote_types(a.dtype, np.dtype(str(b.dtype).replace("torch.", "")))
+    if dt not in (np.float32, np.float64, np.complex64, np.complex128):
+        raise TypeError(f"spmm supports float32/float64/complex64/complex128, got {dt}")
+    a = a.astype(dt)
+    tdt = a.data.dtype
+    b = b.to(device=dev, dtype=tdt)
+    lc = None
+    if c is not None:
+        if not isinstance(c, torch.Tensor):
+            c = torch.from_numpy(np.asarray(c)).to(dev)
+        if c.ndim != 2 or c.shape[0] != m or c.shape[1] != n:
+            raise ValueError("dimension mismatch")
+        if c.dtype != tdt or c.device != dev:
+            raise TypeError("c must be a tensor of the result type on A's device")
+        lc = _dense_layout(c)
+        if lc is None:
+            raise ValueError("c must have unit stride along its rows or its columns")
+    lb = _dense_layout(b, prefer=lc[0] if lc else None)
+    if lb is None or (lc is not None and lb[0] != lc[0]):   # copied into c's order (row-major without c)
+        order = lc[0] if lc else _lib.SPG_ORDER_ROW
+        b = _in_order(b, order)
+        lb = _dense_layout(b, prefer=order)
+    if c is None:        # zeros in b's order (the reference: zeros((m, n), dtype, 'F'), cusparse.py:1486-1487)
+        c = torch.zeros((m, n), dtype=tdt, device=dev) if lb[0] == _lib.SPG_ORDER_ROW \
+            else torch.zeros((n, m), dtype=tdt, device=dev).t()
+        lc = _dense_layout(c, prefer=lb[0])
+    if a.nnz == 0:       # the reference fills 0 (cusparse.py:1490-1492)
+        c.fill_(0)
+        return c
+    h = _handle_for(a)
+    va = _csr_view(a)
+    vb, vc = _dense_view(b, *lb), _dense_view(c, *lc)
+    al, be = _alpha_of(tdt, alpha), _alpha_of(tdt, beta)
+    check(h.lib.spg_spmm(h.ptr, ctypes.byref(va), ctypes.byref(vb), ctypes.byref(al), ctypes.byref(be),
+                         ctypes.byref(vc)), "spg_spmm")
+    return c
+
+
 def num_products(a: csr_matrix, b: csr_matrix) -> int:
     """P = number of scalar products of A.B (cusparseSpGEMM_getNumProducts); GFLOPS = 2P/t."""
     h = _handle_for(a)
@@ -488,5 +586,5 @@ def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float 
         torch.cuda.current_stream(a.device).synchronize()
 
 
-__all__ = ["spgemm", "spmv", "check_availability", "num_products", "validate_csr", "SpgError",
+__all__ = ["spgemm", "spmv", "spmm", "check_availability", "num_products", "validate_csr", "SpgError",
            "last_stats"]

@@ -6,7 +6,8 @@ Mirrors the part of ``cupyx.scipy.sparse`` that the reference's hot path goes th
   f32/f64 ``data`` (modify_src/cupy-src/cupyx/scipy/sparse/_compressed.py:229-230,286-287
   force int32; int64 is added so configs with nnz >= 2**31 are representable);
 * ``A @ B`` dispatch: ``__matmul__`` -> ``__mul__`` -> ``sum_duplicates()`` on both operands
-  -> ``spgemm`` (_base.py:130-134, _csr.py:151-166);
+  -> ``spgemm`` (_base.py:130-134, _csr.py:151-166); a dense right operand goes to ``spmv``
+  (1-D, _csr.py:190-216) or ``spmm`` (2-D, _csr.py:217-225);
 * ``has_canonical_format`` evaluated on the device (the reference's
   ``_has_canonical_format_kern``, _compressed.py:177-192, here ``spg_validate_csr``);
 * ``csc_matrix`` / ``coo_matrix`` operands of ``@`` are converted to CSR first
@@ -214,7 +215,8 @@ class csr_matrix(_SparseBase):
     # ------------------------------------------------------------------ products
     def __mul__(self, other):
         """CSR x sparse: CuPy's _csr.py:151-166 order -- canonicalise both, then spgemm.
-        CSR x dense vector (_csr.py:190-216): canonicalise, then spmv."""
+        CSR x dense vector (_csr.py:190-216): canonicalise, then spmv.
+        CSR x dense matrix (_csr.py:217-225): canonicalise, then spmm."""
         from . import cusparse
         if isinstance(other, (csc_matrix, coo_matrix)):
             other = other.tocsr()
@@ -225,6 +227,11 @@ class csr_matrix(_SparseBase):
         if _is_vector(other):
             self.sum_duplicates()
             return cusparse.spmv(self, other)
+        if _is_matrix(other):
+            self.sum_duplicates()
+            return cusparse.spmm(self, other)
+        if _is_dense(other) and other.ndim > 2:
+            raise ValueError("could not interpret dimensions")
         return NotImplemented
 
     def transpose_csr(self) -> "csr_matrix":
@@ -246,8 +253,16 @@ class csr_matrix(_SparseBase):
                 f"{self.nnz} stored elements on {self.device}>")
 
 
+def _is_dense(x) -> bool:
+    return isinstance(x, (torch.Tensor, np.ndarray))
+
+
 def _is_vector(x) -> bool:
-    return (isinstance(x, torch.Tensor) or isinstance(x, np.ndarray)) and x.ndim == 1
+    return _is_dense(x) and x.ndim == 1
+
+
+def _is_matrix(x) -> bool:
+    return _is_dense(x) and x.ndim == 2
 
 
 class coo_matrix(_SparseBase):
@@ -255,10 +270,13 @@ class coo_matrix(_SparseBase):
     format = "coo"
 
     def __matmul__(self, other):
-        """COO x dense vector -> spmv (through CSR)."""
+        """COO x dense vector -> spmv, x dense matrix -> spmm (through CSR)."""
         if _is_vector(other):
             from . import cusparse
             return cusparse.spmv(self, other)
+        if _is_matrix(other):
+            from . import cusparse
+            return cusparse.spmm(self, other)
         return super().__matmul__(other)
 
     def __init__(self, arg1, shape=None, device=None):
@@ -301,10 +319,14 @@ class csc_matrix(_SparseBase):
     format = "csc"
 
     def __matmul__(self, other):
-        """CSC x dense vector -> spmv (cusparse.py:1395-1401: csc.T is CSR, transposed op)."""
+        """CSC x dense vector -> spmv, x dense matrix -> spmm (cusparse.py:1395-1401,
+        :1467-1473: csc.T is CSR, transposed op)."""
         if _is_vector(other):
             from . import cusparse
             return cusparse.spmv(self, other)
+        if _is_matrix(other):
+            from . import cusparse
+            return cusparse.spmm(self, other)
         return super().__matmul__(other)
 
     def __init__(self, arg1, device=None):
