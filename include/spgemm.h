@@ -44,6 +44,11 @@
  *     bit-identical to scipy after dropping exact zeros and sorting columns, and identical
  *     from run to run.  Structural entries are kept (cuSPARSE semantics): an entry whose
  *     sum cancels to 0 is stored as an explicit 0.  C's columns are sorted ascending.
+ *     Special values: the match with scipy is bit for bit for +-0, denormals and +-inf as
+ *     well (nothing is flushed, no shortcut is taken on a value: alpha = 0 still gives
+ *     0 * inf = NaN and 0 * (-x) = -0.0), and a component -- a real value, or the real or
+ *     imaginary part of a complex one -- is NaN exactly where scipy's is.  The sign and
+ *     payload of a NaN are unspecified.  The same holds for spg_spmv and spg_spmm.
  */
 #ifndef MI355_SPGEMM_H
 #define MI355_SPGEMM_H
@@ -245,7 +250,9 @@ spg_status_t spg_validate_csr(spg_handle_t handle, const spg_csr_t *M, int *is_c
  * `capacity` entries written; chunk_rows may be NULL when capacity is 0).  lds_ordered 1
  * when fp64 / complex128 tiles run the ordered-LDS-add kernels -- the handle's device check at
  * spg_create found the ordering they rely on -- and 0 when they fall back to owner rounds
- * (same results).  record_group (tile path): numeric tiles per VALUE TILE -- B's records are
+ * (same results); for fp32 it is 1 when dense tiles run the entry-run kernel with its ordered
+ * ds_add_f32 (the device check's fp32 half passed and B's segments are long enough), 0 on
+ * owner rounds; complex64 always 0.  record_group (tile path): numeric tiles per VALUE TILE -- B's records are
  * laid out per group of that many adjacent tiles (1: plain tile-major); the value-tile API
  * below works in value tiles of tile_width * record_group columns, ceil(tiles_per_row /
  * record_group) of them. */

@@ -262,3 +262,28 @@ DEFINE_SPMV(double, f64)
 DEFINE_SPMV(float, f32)
 DEFINE_SPMV(orc_c64, c64)
 DEFINE_SPMV(orc_c128, c128)
+
+/* CSR x dense matrix, both row-major (scipy `csr_matvecs`, reached from csr_matrix @ 2-D
+ * ndarray -> _matmul_multivector): Y[i, :] starts at 0 and takes a_ij * X[j, :] entry by
+ * entry in A's stored order -- csr_matvec's rule for every column of X; then Y = alpha * Y
+ * when alpha != 1. */
+#define DEFINE_SPMM(T, SUF)                                                                 \
+    void orc_spmm_##SUF(int64_t n_row, int64_t n_vecs, const int64_t *Ap, const int32_t *Aj, \
+                        const T *Ax, const T *X, T alpha, T *Y)                             \
+    {                                                                                       \
+        for (int64_t i = 0; i < n_row; ++i) {                                               \
+            T *y = Y + n_vecs * i;                                                          \
+            for (int64_t c = 0; c < n_vecs; ++c) y[c] = zero_##SUF();                       \
+            for (int64_t jj = Ap[i]; jj < Ap[i + 1]; ++jj) {                                \
+                const T a = Ax[jj];                                                         \
+                const T *x = X + n_vecs * (int64_t)Aj[jj];                                  \
+                for (int64_t c = 0; c < n_vecs; ++c) y[c] = add_##SUF(y[c], mul_##SUF(a, x[c])); \
+            }                                                                               \
+            if (!one_##SUF(alpha))                                                          \
+                for (int64_t c = 0; c < n_vecs; ++c) y[c] = mul_##SUF(alpha, y[c]);         \
+        }                                                                                   \
+    }
+DEFINE_SPMM(double, f64)
+DEFINE_SPMM(float, f32)
+DEFINE_SPMM(orc_c64, c64)
+DEFINE_SPMM(orc_c128, c128)

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <vector>
 
@@ -344,6 +345,15 @@ spg_status_t hip_fail(spg_handle_t h, hipError_t e) {
 // k_lds_order_check runs LDSCHK_TRIALS trials of two ds_add_f64 instructions from all 64 lanes
 // into 4 slots with operands whose rounded sums depend on the order; the host replays them in
 // (instruction, lane) order.  Any bit difference sets *ordered = false.
+// Every eighth trial (one operand in eight) holds only denormals of T, +-[1,2) * 2^-k * min(T)
+// with k in [1, 20], and a sixteenth of those operands are +-0.0: beside a normal operand a
+// denormal is absorbed whether the adder keeps it or not, so only sums made of denormals alone
+// (they stay denormal or just cross into the normal range) show an LDS add that flushes its
+// inputs or its result.  Such a device takes the owner rounds too.  The +-0.0 operands only
+// thin those sums out: a slot starts at +0.0 and takes about 32 operands, so no sum here ends
+// as -0.0 and the sign of a zero result is NOT checked (the GPU parity tests on special values
+// check it end to end).  No inf / NaN: the replay compares with memcmp, and NaN payloads differ
+// between the host and the device.
 template <typename T>
 hipError_t lds_order_check_t(bool* ordered) {
     constexpr int N = LDSCHK_TRIALS * 2 * WAVE;
@@ -354,7 +364,13 @@ hipError_t lds_order_check_t(bool* ordered) {
     for (int i = 0; i < N; ++i) {
         const uint64_t r = next();
         const double m = 1.0 + (double)(r >> 11) * (1.0 / 9007199254740992.0);   // [1, 2)
-        v[i] = (T)std::ldexp((r & 1) ? -m : m, (int)((r >> 1) % 81) - 40);
+        const bool denormal_trial = (i / (2 * WAVE)) % 8 == 7;
+        if (!denormal_trial)
+            v[i] = (T)std::ldexp((r & 1) ? -m : m, (int)((r >> 1) % 81) - 40);
+        else if (((r >> 20) & 15) == 0)
+            v[i] = (r & 1) ? -(T)0 : (T)0;
+        else   // min(T) = 2^(min_exponent - 1)
+            v[i] = (T)std::ldexp((r & 1) ? -m : m, std::numeric_limits<T>::min_exponent - 2 - (int)((r >> 1) % 20));
         slot[i] = (int)((r >> 8) & 3);
     }
     T *dv = nullptr, *dout = nullptr;
@@ -2194,8 +2210,11 @@ spg_status_t spg_plan_info(spg_plan_t p, spg_plan_info_t* info, int64_t* chunk_r
     const bool chunked = p->alg == SPG_ALG3 && p->chunk_rows.size() > 1;
     info->n_chunks = chunked ? (int64_t)p->chunk_rows.size() - 1 : 1;
     // fp64 / complex128 tiles on the ordered-LDS kernels (k_tile_dn / k_tile_sp), or k_tile's
-    // owner rounds (the handle's LDS check failed, or SPG_LDS_ORDERED=0)
+    // owner rounds (the handle's LDS check failed, or SPG_LDS_ORDERED=0); fp32 dense tiles on the
+    // entry runs of k_tile_dn<float, .., 1024> (ds_add_f32: the handle's fp32 check, the segment
+    // rule and SPG_F32_RUNS, as tile_numeric decides), or k_tile's owner rounds
     info->lds_ordered = p->use_tile && p->lean && (p->A.value_type == SPG_R_64F || p->A.value_type == SPG_C_64F) ? 1 : 0;
+    if (tile_dense(*p) && fp32_runs(*p)) info->lds_ordered = 1;
     for (int64_t i = 0; i < std::min<int64_t>(capacity, info->n_chunks + 1); ++i)
         chunk_rows[i] = chunked ? p->chunk_rows[(size_t)i] : (i == 0 ? 0 : p->A.rows);
     return SPG_STATUS_SUCCESS;

@@ -43,6 +43,7 @@ template <typename R> __device__ __forceinline__ void lds_add(cplx<R>* p, cplx<R
 // Run-time check of the two properties above (spg_create, lds_order_check in spgemm.hip):
 // LDSCHK_TRIALS trials; in each, two ds_add_f64 (ds_add_f32) instructions from all 64 lanes into 4
 // slots (v and slot indexed [trial][instruction][lane]); the slots' sums go to out[trial][4].
+// Every eighth trial's operands are denormals (and a few zeros) only: a flushing adder fails the check.
 constexpr int LDSCHK_TRIALS = 64;
 template <typename T>
 __global__ __launch_bounds__(WAVE) void k_lds_order_check(const T* __restrict__ v, const int* __restrict__ slot,

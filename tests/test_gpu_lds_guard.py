@@ -98,7 +98,7 @@ def _check_all(got, algs=(2, 3)):
 def test_device_check_finds_ordered_lds():
     """On MI355X the check passes: fp64 tile plans run the ordered-LDS kernels, and the shapes
     keep their lean geometries (2048-column dense tiles, 8192-column sparse tiles)."""
-    from spmm_amd import cusparse
+    from spmm_amd import cusparse, gen
     from spmm_amd.sparse import csr_matrix
     cases = {name: (A, B) for name, A, B, _ in _cases()}
     widths = {"dense2048_shape": (2048, True), "sparse8192_shape": (8192, False)}
@@ -107,6 +107,19 @@ def test_device_check_finds_ordered_lds():
         assert info["path"] == "tile" and info["lds_ordered"], (name, info)
         if name in widths:
             assert (info["tile_width"], info["dense_tiles"]) == widths[name], (name, info)
+    # the fp32 half of the check (ds_add_f32): fp32 dense tiles of long B segments
+    # (test_tile_fp32_entry_runs' shape) run k_tile_dn<float, .., 1024>'s entry runs, and
+    # SPG_F32_RUNS=0 (read per plan) sends them to the owner rounds
+    A, B = gen.scipy_pair(2048, 0.2, seed=7, dtype=np.float32)
+    dA, dB = csr_matrix(A, device="cuda:0"), csr_matrix(B, device="cuda:0")
+    info = cusparse.plan_info(dA, dB, alg=2)
+    assert info["path"] == "tile" and info["dense_tiles"] and info["tile_width"] == 1024, info
+    assert info["lds_ordered"], info
+    os.environ["SPG_F32_RUNS"] = "0"
+    try:
+        assert not cusparse.plan_info(dA, dB, alg=2)["lds_ordered"]
+    finally:
+        del os.environ["SPG_F32_RUNS"]
 
 
 def test_owner_round_fallback_bitexact(tmp_path):
