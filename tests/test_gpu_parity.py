@@ -284,14 +284,22 @@ def _skewed(rng, rows, k, n, dense_rows, base_density, b_density, dtype=np.float
 
 
 def test_tile_path_windows_and_skew():
-    """Wide-row (row, column tile) path: 4096-column tiles whose dense rows need several
-    LDS windows per tile, empty A rows, a ragged last tile (n % 4096 != 0), alpha != 1,
-    every algorithm (ALG3 with many chunks)."""
+    """Wide-row (row, column tile) path with skewed rows: C rows expected 21 % dense over 100003
+    columns, which want_tile widens from 4096- to 8192-column sparse tiles in record groups of 8
+    (k_tile_sp<double, SpCfgRG, 8>; 13 tiles, so the second group has three padding tiles).  The
+    dense rows need several LDS windows per tile; empty A rows, a ragged last tile
+    (n % 8192 != 0), alpha != 1, every algorithm (ALG3 with many chunks).  plan_info states the
+    geometry (4096-column sparse tiles are run by tests/test_gpu_instantiations.py)."""
+    from spmm_amd import cusparse
+    from spmm_amd.sparse import csr_matrix
     rng = np.random.default_rng(31)
     A, B = _skewed(rng, 384, 4096, 100003, dense_rows=[0, 17, 200, 383], base_density=0.05,
                    b_density=0.001)
     ref = oracle.spgemm(A, B, alpha=-0.75, keep_zeros=True, sort=True)
     assert np.diff(ref[0]).max() > 4 * 1024        # some tiles hold several windows
+    info = cusparse.plan_info(csr_matrix(A, device=_dev()), csr_matrix(B, device=_dev()), alg=2)
+    assert (info["path"], info["tile_width"], info["tiles_per_row"], info["dense_tiles"], info["lds_ordered"],
+            info["record_group"]) == ("tile", 8192, 13, False, True, 8), info
     for alg, cf in [(1, 0.2), (2, 0.2), (3, 0.2), (3, 0.02)]:
         _assert_same(_gpu(A, B, alg=alg, alpha=-0.75, cf=cf), ref)
 
@@ -592,6 +600,13 @@ def test_complex_bitexact(dt, m, k, n, density, alg):
     B = _cplx_random(k, n, density, rng, dt)
     alpha = 0.5 - 0.25j
     _assert_same(_gpu(A, B, alg=alg, alpha=alpha), oracle.spgemm(A, B, alpha=alpha, keep_zeros=True, sort=True))
+    # each shape reaches the path its comment names (the tile shape: 1024-column dense tiles)
+    from spmm_amd import cusparse
+    from spmm_amd.sparse import csr_matrix
+    info = cusparse.plan_info(csr_matrix(A, device=_dev()), csr_matrix(B, device=_dev()), alg=alg)
+    assert info["path"] == {2048: "short", 600: "tile", 300: "general"}[m], info
+    if m == 600:
+        assert info["tile_width"] == 1024 and info["dense_tiles"] and info["lds_ordered"] == (dt == np.complex128), info
 
 
 def test_upstream_testspgemm_complex():
