@@ -220,6 +220,26 @@ typedef struct {
 spg_status_t spg_spmm(spg_handle_t handle, const spg_csr_t *A, const spg_dense_t *B,
                       const void *alpha, const void *beta, spg_dense_t *C);
 
+/* Transpose / format conversion: AT = A^T as CSR (equivalently: A in CSC).  AT->rows == A->cols,
+ * AT->cols == A->rows, AT->nnz == A->nnz, same value type and same indptr type as A (else
+ * SPG_STATUS_INVALID_VALUE).  Writes AT->indptr (A->cols + 1 entries), AT->indices (the source
+ * rows) and AT->values.  Stable: the entries of output row j keep A's stored (row-major) entry
+ * order -- scipy's csr_tocsc -- so a canonical A gives a canonical AT, and an A with unsorted rows
+ * or duplicates gives exactly scipy's tocsc(): duplicates kept, in stored order; identical from
+ * run to run.  Values are moved, never computed on: bit for bit, NaN sign and payload included
+ * (stricter than the products' NaN rule above).  A's indices must lie in [0, cols) (not checked);
+ * output arrays overlapping A's are undefined.  rows == 0, cols == 0 and nnz == 0 succeed and leave
+ * an all-zero AT->indptr.
+ *   workspace == NULL: size query into *workspace_bytes (host arithmetic, nothing launched).
+ *   workspace != NULL: *workspace_bytes must be >= the queried size (else INVALID_VALUE).
+ * Stream-ordered; does not wait; device memory is the caller's workspace only.  NULL A, AT,
+ * workspace_bytes or a needed array: SPG_STATUS_INVALID_VALUE.  Timed under SPG_PHASE_LAYOUT
+ * (its scans under SPG_PHASE_SCAN).  (cusparseCsr2cscEx2 as called by cupyx.cusparse.csr2csc,
+ * cupy-src/cupyx/cusparse.py:1014-1065; csc2csr, :1092-1113, is the same call on the CSC arrays.
+ * Added within 0.2.0: a caller detects it by symbol lookup.) */
+spg_status_t spg_csr2csc(spg_handle_t handle, const spg_csr_t *A, spg_csr_t *AT,
+                         size_t *workspace_bytes, void *workspace);
+
 /* ALG1 single pass: after spg_symbolic, C's column indices and values may already sit
  * compact in the workspace (nnzC entries at *indices / *values; NULL otherwise).  A
  * caller may hand exactly these pointers to spg_numeric as C->indices / C->values: the
@@ -351,7 +371,8 @@ typedef enum {
     SPG_PHASE_SPMV = 7,       /* k_spmv / k_spmm                                    */
     SPG_PHASE_LAYOUT = 8,     /* the tile path's B re-layout: once per plan          */
                               /* (k_tile_index, k_bt_count, k_bj16, k_bt_pack) and   */
-                              /* per tile group (k_bt_fill, spg_numeric_tiles)        */
+                              /* per tile group (k_bt_fill, spg_numeric_tiles);       */
+                              /* spg_csr2csc's passes (k_tr_hist, k_tr_scatter)       */
     SPG_NUM_PHASES = 9
 } spg_phase_t;
 

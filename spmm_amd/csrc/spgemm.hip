@@ -24,6 +24,7 @@
 #include "spgemm_spmv.hpp"
 #include "spgemm_row.hpp"
 #include "spgemm_spmm.hpp"
+#include "spgemm_transpose.hpp"
 
 using namespace spg;
 
@@ -2111,6 +2112,141 @@ spg_status_t spg_spmm(spg_handle_t h, const spg_csr_t* A, const spg_dense_t* B, 
         std::memcpy(&be, beta, sizeof(T));
         return i64 ? spmm_launch<T, int64_t>(h, *A, *B, al, be, *C) : spmm_launch<T, int32_t>(h, *A, *B, al, be, *C);
     });
+}
+
+// ----------------------------------------------------------------------------- spg_csr2csc
+extern "C++" {
+namespace {
+
+// Workspace carve of spg_csr2csc (offsets from the 256-byte aligned base).
+struct TrLayout {
+    int passes = 1;            // 8-bit digit passes: the bytes of cols - 1 (at least one)
+    int64_t chunks = 0;        // wave chunks of TR_CHUNK entries
+    int nbuf = 0;              // ping-pong record buffers the passes need (0, 1 or 2)
+    size_t scalars = 0, status = 0, table = 0, skeys = 0, buf[2] = {0, 0};
+    size_t keys = 0, rowids = 0, pos = 0;   // inside one record buffer
+    size_t total = 0;          // bytes to ask for (256 of slack for the base alignment)
+};
+
+TrLayout tr_layout(const spg_csr_t& A) {
+    TrLayout L;
+    const size_t ips = A.indptr_type == SPG_INDEX_64I ? 8 : 4;
+    const uint64_t top = A.cols > 0 ? (uint64_t)(A.cols - 1) : 0;
+    L.passes = top >= (1ull << 24) ? 4 : top >= (1ull << 16) ? 3 : top >= (1ull << 8) ? 2 : 1;
+    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
+    L.nbuf = std::min(L.passes - 1, 2);
+    size_t off = 0;
+    L.scalars = off;
+    off += align_up(16 * sizeof(int64_t));
+    L.status = off;
+    off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(TR_RADIX * L.chunks) + 1));
+    L.table = off;
+    off += align_up(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
+    L.skeys = off;   // the sorted columns (the last pass -> k_tr_indptr)
+    off += align_up(sizeof(int32_t) * (size_t)A.nnz);
+    L.keys = 0;
+    L.rowids = align_up(sizeof(int32_t) * (size_t)A.nnz);
+    L.pos = 2 * L.rowids;
+    const size_t rec = L.pos + align_up(ips * (size_t)A.nnz);
+    for (int b = 0; b < L.nbuf; ++b) {
+        L.buf[b] = off;
+        off += rec;
+    }
+    L.total = off + 256;
+    return L;
+}
+
+template <typename IP>
+spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrLayout& L, char* ws) {
+    const int64_t nnz = A.nnz, chunks = L.chunks;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    unsigned long long* status = (unsigned long long*)(ws + L.status);
+    IP* table = (IP*)(ws + L.table);
+    IP* ATp = (IP*)AT.indptr;
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    const int32_t* kin = (const int32_t*)A.indices;
+    const int32_t* rin = nullptr;
+    const IP* pin = nullptr;
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = 8 * p;
+        const bool first = p == 0, last = p == L.passes - 1;
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP>, grid, block, nnz, chunks, kin, shift, table);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
+        char* out = last ? nullptr : ws + L.buf[p & 1];
+        int32_t* kout = last ? (int32_t*)(ws + L.skeys) : (int32_t*)(out + L.keys);
+        int32_t* rout = last ? nullptr : (int32_t*)(out + L.rowids);
+        IP* pout = last ? nullptr : (IP*)(out + L.pos);
+        if (!last) {
+            using V = uint32_t;   // (no value is touched before the last pass)
+            if (first)
+                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, false>, grid, block, nnz, chunks, shift,
+                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
+                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
+            else
+                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, false>, grid, block, nnz, chunks, shift,
+                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
+                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
+        } else {
+            auto run_last = [&](auto vtag) {
+                using V = decltype(vtag);
+                if (first)
+                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, true>, grid, block, nnz, chunks,
+                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
+                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
+                else
+                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, true>, grid, block, nnz, chunks,
+                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
+                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
+            };
+            switch (vbytes(A.value_type)) {
+                case 4: run_last(TrBits<4>::type{}); break;
+                case 8: run_last(TrBits<8>::type{}); break;
+                default: run_last(TrBits<16>::type{}); break;
+            }
+        }
+        SPG_LAUNCHED(h);
+        kin = kout;
+        rin = rout;
+        pin = pout;
+    }
+    // (kin: the sorted columns the last pass left)
+    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
+    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP>, dim3(pgrid), dim3(256), nnz, A.cols, kin, ATp);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+}  // namespace
+}  // extern "C++"
+
+spg_status_t spg_csr2csc(spg_handle_t h, const spg_csr_t* A, spg_csr_t* AT, size_t* workspace_bytes,
+                         void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!A || !AT || !workspace_bytes) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = check_csr(A);
+    if (st) return st;
+    if (A->rows > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;   // AT's int32 indices are A's rows
+    if (AT->rows != A->cols || AT->cols != A->rows || AT->nnz != A->nnz) return SPG_STATUS_INVALID_VALUE;
+    if (AT->value_type != A->value_type || AT->indptr_type != A->indptr_type) return SPG_STATUS_INVALID_VALUE;
+    if (A->nnz > 0 && (A->rows == 0 || A->cols == 0)) return SPG_STATUS_INVALID_VALUE;
+    const TrLayout L = tr_layout(*A);
+    if (!workspace) {   // size query: host arithmetic only
+        *workspace_bytes = L.total;
+        return SPG_STATUS_SUCCESS;
+    }
+    if (*workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (!AT->indptr || (A->nnz > 0 && (!AT->indices || !AT->values))) return SPG_STATUS_INVALID_VALUE;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    const bool i64 = A->indptr_type == SPG_INDEX_64I;
+    if (A->nnz == 0) {   // an all-zero row pointer
+        SPG_HIP(h, hipMemsetAsync(AT->indptr, 0, (i64 ? 8 : 4) * (size_t)(A->cols + 1), h->stream));
+        return SPG_STATUS_SUCCESS;
+    }
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    return i64 ? tr_run<int64_t>(h, *A, *AT, L, ws) : tr_run<int32_t>(h, *A, *AT, L, ws);
 }
 
 spg_status_t spg_result_in_workspace(spg_plan_t p, void** indices, void** values) {

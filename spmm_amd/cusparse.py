@@ -58,7 +58,7 @@ def check_availability(name: str) -> bool:
     """True when the named routine can run here (a gfx950 device and the built library).
     Memoized like the reference's ``@_util.memoize()`` check (cusparse.py:169-186)."""
     global _available
-    if name not in ("spgemm", "spmv", "spmm", "validate_csr"):
+    if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr"):
         raise ValueError(f"No available version information specified for {name}")
     if _available is None:
         try:
@@ -392,7 +392,9 @@ def spmv(a, x, y=None, alpha=1, beta=0, transa=False):
 
     A is csr_matrix, csc_matrix or coo_matrix (CSC goes through its transpose as the
     reference does, COO through CSR).  x, y are 1-D tensors (or numpy arrays, uploaded).
-    With CSR A, alpha = 1 and beta = 0 the result equals scipy's ``A @ x`` bit for bit.
+    With CSR A, alpha = 1 and beta = 0 the result equals scipy's ``A @ x`` bit for bit; so do
+    ``transa=True`` and a CSC operand against scipy's ``A.T @ x`` / ``A @ x``: the transpose is
+    spg_csr2csc's stable counting sort, scipy's own (csr_tocsc), so the sums keep scipy's order.
     """
     from .sparse import coo_matrix, csc_matrix
     if not check_availability("spmv"):
@@ -476,7 +478,8 @@ def spmm(a, b, c=None, alpha=1, beta=0, transa=False, transb=False):
     row-major or column-major layout, read from their strides; ``transb`` is a view and moves
     no data.  The reference takes F-contiguous arrays only; both orders run here, and the
     result has b's order (c's when c is given).  With CSR A, alpha = 1 and beta = 0 the result
-    equals scipy's ``A @ B`` bit for bit.
+    equals scipy's ``A @ B`` bit for bit; so do ``transa=True`` and a CSC operand against scipy's
+    ``A.T @ B`` / ``A @ B`` (the transpose is spg_csr2csc's stable counting sort, as in scipy).
     """
     from .sparse import coo_matrix, csc_matrix
     if not check_availability("spmm"):
@@ -539,6 +542,72 @@ def spmm(a, b, c=None, alpha=1, beta=0, transa=False, transb=False):
     return c
 
 
+def has_csr2csc() -> bool:
+    """True when the loaded library exports spg_csr2csc (added within 0.2.0: an older
+    development build lacks it, and the containers then keep their torch conversion)."""
+    return hasattr(_lib.load(), "spg_csr2csc")
+
+
+def _csr2csc_arrays(data, indices, indptr, rows: int, cols: int):
+    """(data, indices, indptr) of the transpose of the rows x cols CSR arrays, on spg_csr2csc:
+    the CSC arrays of the same matrix.  indptr comes back int32 whenever nnz fits."""
+    dev = data.device
+    nnz = int(data.numel())
+    ipd = torch.int32 if nnz <= 2 ** 31 - 1 else torch.int64
+    out_data = torch.empty(nnz, dtype=data.dtype, device=dev)
+    out_indices = torch.empty(nnz, dtype=torch.int32, device=dev)
+    if nnz == 0:         # the reference fills zeros without a call (cusparse.py:1023-1024)
+        return out_data, out_indices, torch.zeros(cols + 1, dtype=ipd, device=dev)
+    data, indices, indptr = data.contiguous(), indices.contiguous(), indptr.to(ipd).contiguous()
+    out_indptr = torch.empty(cols + 1, dtype=ipd, device=dev)
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _lib.get_handle(idx)
+    h.set_stream(_current_stream_ptr(idx))
+    va = SpgCsr(rows, cols, nnz, indptr.data_ptr(), indices.data_ptr(), data.data_ptr(), _IT[ipd], _VT[data.dtype])
+    vt = SpgCsr(cols, rows, nnz, out_indptr.data_ptr(), out_indices.data_ptr(), out_data.data_ptr(), _IT[ipd],
+                _VT[data.dtype])
+    ws_bytes = ctypes.c_size_t(0)
+    check(h.lib.spg_csr2csc(h.ptr, ctypes.byref(va), ctypes.byref(vt), ctypes.byref(ws_bytes), None), "spg_csr2csc")
+    # workspace from torch's caching allocator on the current stream, as in _spgemm
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    check(h.lib.spg_csr2csc(h.ptr, ctypes.byref(va), ctypes.byref(vt), ctypes.byref(ws_bytes),
+                            ctypes.c_void_p(ws.data_ptr())), "spg_csr2csc")
+    return out_data, out_indices, out_indptr
+
+
+def csr2csc(x):
+    """CSR -> CSC of the same matrix -- the drop-in for ``cupyx.cusparse.csr2csc``
+    (modify_src/cupy-src/cupyx/cusparse.py:1014-1035), on ``spg_csr2csc``.  Stable: every
+    column keeps x's stored entry order, so the arrays equal scipy's ``tocsc()`` array for array
+    (duplicates kept), and the values are moved bit for bit."""
+    from .sparse import csc_matrix
+    if not check_availability("csr2csc"):
+        raise RuntimeError("csr2csc is not available.")
+    if not isinstance(x, csr_matrix):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError("csr2csc needs device-resident operands")
+    m, n = x.shape
+    data, indices, indptr = _csr2csc_arrays(x.data, x.indices, x.indptr, m, n)
+    return csc_matrix((data, indices, indptr), shape=x.shape, canonical=True if x._canonical is True else None)
+
+
+def csc2csr(x):
+    """CSC -> CSR of the same matrix -- the drop-in for ``cupyx.cusparse.csc2csr``
+    (modify_src/cupy-src/cupyx/cusparse.py:1092-1113): spg_csr2csc on the CSC arrays read as
+    the CSR of the transpose.  Equals scipy's ``tocsr()`` array for array."""
+    from .sparse import csc_matrix
+    if not check_availability("csc2csr"):
+        raise RuntimeError("csr2csc is not available.")
+    if not isinstance(x, csc_matrix):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError("csc2csr needs device-resident operands")
+    m, n = x.shape
+    data, indices, indptr = _csr2csc_arrays(x.data, x.indices, x.indptr, n, m)
+    return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True if x._canonical is True else None)
+
+
 def num_products(a: csr_matrix, b: csr_matrix) -> int:
     """P = number of scalar products of A.B (cusparseSpGEMM_getNumProducts); GFLOPS = 2P/t."""
     h = _handle_for(a)
@@ -586,5 +655,5 @@ def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float 
         torch.cuda.current_stream(a.device).synchronize()
 
 
-__all__ = ["spgemm", "spmv", "spmm", "check_availability", "num_products", "validate_csr", "SpgError",
+__all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "check_availability", "num_products", "validate_csr", "SpgError",
            "last_stats"]

@@ -11,10 +11,14 @@ Mirrors the part of ``cupyx.scipy.sparse`` that the reference's hot path goes th
 * ``has_canonical_format`` evaluated on the device (the reference's
   ``_has_canonical_format_kern``, _compressed.py:177-192, here ``spg_validate_csr``);
 * ``csc_matrix`` / ``coo_matrix`` operands of ``@`` are converted to CSR first
-  (_csr.py:167-184).
+  (_csr.py:167-184);
+* ``csr_matrix.tocsc()`` / ``.transpose()`` / ``.T`` (_csr.py:512-533) and
+  ``csc_matrix((data, indices, indptr), shape=...)``.
 
-Format conversions and duplicate summing run as torch device ops; the multiply itself runs
-only in libmi355_spgemm.so.
+CSR <-> CSC conversion of device tensors runs in libmi355_spgemm.so (``spg_csr2csc``, a stable
+counting sort: scipy's own order, so transposed products stay bit-exact with scipy); COO
+conversion and duplicate summing run as torch device ops, as does CSR <-> CSC for tensors that
+are not on a GPU.  The multiply itself runs only in the library.
 """
 from __future__ import annotations
 
@@ -38,6 +42,26 @@ def _as_tensor(x, dtype: torch.dtype, device) -> torch.Tensor:
 def _default_device():
     return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
         else torch.device("cpu")
+
+
+def _engine_transposes(t: torch.Tensor) -> bool:
+    """CSR <-> CSC of these tensors runs on spg_csr2csc: they sit on a GPU and the loaded
+    library exports the symbol (otherwise the torch conversion serves)."""
+    if t.device.type != "cuda":
+        return False
+    from . import cusparse
+    return cusparse.has_csr2csc()
+
+
+def _stable_by_index(data, indices, indptr, n_major: int, n_minor: int):
+    """The torch form of scipy's csr_tocsc: the (data, indices, indptr) of the other
+    compressed format, every output segment in stored entry order, duplicates kept."""
+    counts = (indptr[1:] - indptr[:-1]).to(torch.int64)
+    major = torch.repeat_interleave(torch.arange(n_major, device=data.device), counts)
+    _, order = torch.sort(indices.to(torch.int64), stable=True)
+    ipd = torch.int32 if data.numel() <= INT32_MAX else torch.int64
+    return (data[order].contiguous(), major[order].to(torch.int32),
+            _indptr_from_rows(indices.to(torch.int64), n_minor, ipd))
 
 
 class _SparseBase:
@@ -234,9 +258,42 @@ class csr_matrix(_SparseBase):
             raise ValueError("could not interpret dimensions")
         return NotImplemented
 
-    def transpose_csr(self) -> "csr_matrix":
-        """A^T as a canonical CSR matrix (through COO with rows and columns swapped)."""
+    def tocsc(self, copy=False) -> "csc_matrix":
+        """The same matrix in CSC, array for array what scipy's ``tocsc()`` gives (every
+        column in stored entry order, duplicates kept): spg_csr2csc for device tensors."""
+        if _engine_transposes(self.data):
+            from . import cusparse
+            return cusparse.csr2csc(self)
+        data, indices, indptr = _stable_by_index(self.data, self.indices, self.indptr, *self._shape)
+        return csc_matrix((data, indices, indptr), shape=self._shape,
+                          canonical=True if self._canonical is True else None)
+
+    def transpose(self, axes=None, copy=False) -> "csc_matrix":
+        """The transpose as a csc_matrix over the same arrays (cupyx _csr.py:512-533)."""
+        if axes is not None:
+            raise ValueError("Sparse matrices do not support an 'axes' parameter because "
+                             "swapping dimensions is the only logical permutation.")
         m, n = self._shape
+        arrays = (self.data, self.indices, self.indptr)
+        if copy:
+            arrays = tuple(a.clone() for a in arrays)
+        return csc_matrix(arrays, shape=(n, m), canonical=self._canonical)
+
+    @property
+    def T(self) -> "csc_matrix":
+        return self.transpose()
+
+    def transpose_csr(self) -> "csr_matrix":
+        """A^T as a canonical CSR matrix: spg_csr2csc for device tensors (a canonical A gives a
+        canonical A^T; otherwise duplicates are then summed in stored order, as the torch path
+        does), else through COO with rows and columns swapped."""
+        m, n = self._shape
+        if _engine_transposes(self.data):
+            from . import cusparse
+            t = cusparse.csr2csc(self)
+            out = csr_matrix._from_parts(t.data, t.indices, t.indptr, (n, m), canonical=t._canonical)
+            out.sum_duplicates()
+            return out
         counts = (self.indptr[1:] - self.indptr[:-1]).to(torch.int64)
         rows = torch.repeat_interleave(torch.arange(m, device=self.device), counts)
         return coo_matrix((self.data, (self.indices.to(torch.int64), rows)), shape=(n, m),
@@ -315,7 +372,12 @@ class coo_matrix(_SparseBase):
 
 
 class csc_matrix(_SparseBase):
-    """Compressed-column operand (only what CSR conversion needs)."""
+    """Compressed-column matrix on the device.
+
+    ``csc_matrix(S)``            from a scipy.sparse matrix (uploaded),
+    ``csc_matrix((data, indices, indptr), shape=(m, n))`` from arrays / tensors (tensors of the
+    stored types on the target device are kept as they are, not copied).
+    """
     format = "csc"
 
     def __matmul__(self, other):
@@ -329,13 +391,32 @@ class csc_matrix(_SparseBase):
             return cusparse.spmm(self, other)
         return super().__matmul__(other)
 
-    def __init__(self, arg1, device=None):
+    def __init__(self, arg1, device=None, shape=None, canonical=None):
+        if isinstance(arg1, tuple) and len(arg1) == 3:
+            if shape is None:
+                raise ValueError("shape is required for (data, indices, indptr)")
+            data, indices, indptr = arg1
+            device = torch.device(device) if device is not None else (
+                data.device if isinstance(data, torch.Tensor) else _default_device())
+            ddt = _NP_OF[data.dtype] if isinstance(data, torch.Tensor) else np.asarray(data).dtype
+            self.data = _as_tensor(data, _TORCH_OF[np.dtype(ddt)], device)
+            self.indices = _as_tensor(indices, torch.int32, device)
+            ipd = torch.int32 if self.data.numel() <= INT32_MAX else torch.int64
+            self.indptr = _as_tensor(indptr, ipd, device)
+            self._shape = (int(shape[0]), int(shape[1]))
+            self._canonical = canonical
+            if self.data.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
+                raise TypeError(f"unsupported dtype {self.data.dtype}")
+            if self.indptr.numel() != self._shape[1] + 1:
+                raise ValueError("indptr length must be columns + 1")
+            return
         S = arg1.tocsc()
         device = device or _default_device()
         self.data = _as_tensor(S.data, _TORCH_OF[np.dtype(S.dtype)], device)
         self.indices = _as_tensor(S.indices, torch.int32, device)
         self.indptr = _as_tensor(S.indptr, torch.int64, device)
         self._shape = tuple(int(s) for s in S.shape)
+        self._canonical = True if S.has_canonical_format else None
 
     @property
     def T(self) -> csr_matrix:
@@ -344,8 +425,28 @@ class csc_matrix(_SparseBase):
         ipd = torch.int32 if self.nnz <= INT32_MAX else torch.int64
         return csr_matrix((self.data, self.indices, self.indptr.to(ipd)), shape=(n, m))
 
+    def transpose(self, axes=None, copy=False) -> csr_matrix:
+        """The transpose as a csr_matrix over the same arrays, the canonical flag carried over
+        (cupyx _csc.py transpose)."""
+        if axes is not None:
+            raise ValueError("Sparse matrices do not support an 'axes' parameter because "
+                             "swapping dimensions is the only logical permutation.")
+        out = self.T
+        if copy:
+            out = out.copy()
+        out._canonical = self._canonical
+        return out
+
     def tocsr(self) -> csr_matrix:
+        """The same matrix in CSR: spg_csr2csc for device tensors (a canonical CSC gives a
+        canonical CSR; otherwise duplicates are then summed in stored order, as the torch path
+        does), else through COO."""
         m, n = self._shape
+        if _engine_transposes(self.data):
+            from . import cusparse
+            out = cusparse.csc2csr(self)
+            out.sum_duplicates()
+            return out
         counts = (self.indptr[1:] - self.indptr[:-1]).to(torch.int64)
         cols = torch.repeat_interleave(torch.arange(n, device=self.device), counts)
         return coo_matrix((self.data, (self.indices.to(torch.int64), cols)), shape=(m, n),
