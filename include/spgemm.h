@@ -240,6 +240,59 @@ spg_status_t spg_spmm(spg_handle_t handle, const spg_csr_t *A, const spg_dense_t
 spg_status_t spg_csr2csc(spg_handle_t handle, const spg_csr_t *A, spg_csr_t *AT,
                          size_t *workspace_bytes, void *workspace);
 
+/* Sparse matrix addition: C = alpha*A + beta*B, in two calls like the product -- a structure pass
+ * that writes C's row pointer and returns nnz(C), then a value pass into the caller's C.
+ * (cusparseXcsrgeam2Nnz and cusparse<t>csrgeam2 with its csrgeam2_bufferSizeExt, as called by
+ * cupyx.cusparse.csrgeam2, cupy-src/cupyx/cusparse.py:525-591; reached from A + B and A - B
+ * through cupy-src/cupyx/scipy/sparse/_compressed.py:321-360 and _csr.py:84-96.  Added within
+ * 0.2.0: a caller detects it by symbol lookup.)
+ *   Inputs: A and B canonical CSR (sorted, duplicate-free rows) of the same shape, the same value
+ *     type and the same indptr type.  C's row pointer may be int32 or int64 whatever theirs is.
+ *     C's structure is the union of the two patterns, columns ascending.  nnz(C) counts structural
+ *     entries: an entry that cancels is stored as an explicit 0, so A - A has nnz(A) entries.
+ *   Values: va = alpha == 1 ? a : alpha * a and vb = beta == 1 ? b : beta * b; an entry in both
+ *     patterns gets va + vb, an A-only entry va + 0, a B-only entry 0 + vb; every multiply and
+ *     add separately rounded (no FMA; complex products as (ac - bd) + (ad + bc)i, also for a
+ *     coefficient whose imaginary part is 0).  The added +0 is scipy's: its binary op computes
+ *     an entry one operand lacks as a + 0, which differs from a only in a -0.0 component turning
+ *     into +0.0 (for a real type that is an exact zero; a complex entry can hold one beside a
+ *     nonzero part).  No shortcut is taken on a value: beta == 0 still gives 0 * inf = NaN and
+ *     keeps B's pattern.  The special-value rule is the one above: +-0, denormals and +-inf bit
+ *     for bit, NaN exactly where scipy has it, NaN sign and payload unspecified.  This is scipy's
+ *     (alpha*A) + (beta*B) after dropping exact zeros, and with (alpha, beta) = (1, 1) its A + B.
+ *     The pair (alpha, beta) = (1, -1) is the subtraction A - B, scipy's csr_minus_csr: a - b,
+ *     a - 0 and 0 - b part by part, formed as a + (-b) with b's sign flipped and no product.
+ *     (The complex product (-1, 0) * b would make 0 * inf = NaN in the other part of a b with an
+ *     infinite part, which scipy's A - B does not have and its A + (-1)*B does; every other pair
+ *     with beta == -1, (2, -1) for one, forms that product.)  Identical from run to run.
+ *   spg_csrgeam_nnz, workspace == NULL: size query, *workspace_bytes is set by host arithmetic
+ *     and nothing is launched.  workspace != NULL: *workspace_bytes must be >= the queried size;
+ *     writes C_indptr (A->rows + 1 entries of C_indptr_type) and *nnzC, waiting for the device
+ *     once, for nnzC.  SPG_STATUS_OVERFLOW when nnzC does not fit an int32 C_indptr (*nnzC is
+ *     still set: call again with an int64 array).  A's and B's values are not read.
+ *   spg_csrgeam: takes the workspace exactly as spg_csrgeam_nnz left it, for the same A and B;
+ *     C->indptr is the array that call wrote, C->indices / C->values hold C->nnz = nnzC entries.
+ *     alpha and beta point to one host value each of the operands' value type.  Stream-ordered;
+ *     does not wait.
+ *   Neither call allocates device memory: every device scalar lives in the workspace.
+ *   Status: NULL handle SPG_STATUS_NOT_INITIALIZED (checked first).  SPG_STATUS_INVALID_VALUE
+ *     for a NULL A, B, workspace_bytes or nnzC; a NULL C_indptr with a workspace; a shape,
+ *     value-type or indptr-type mismatch between A and B; a C_indptr_type that is neither index
+ *     type; a workspace below the queried size (spg_csrgeam: or NULL); NULL alpha, beta or C; a C
+ *     that is not A's shape and value type; a NULL array that is needed.
+ *   Degenerate sizes: rows == 0 succeeds without a launch; nnz(A) == 0 and nnz(B) == 0 leave an
+ *     all-zero row pointer; nnz(A) == 0 gives beta*B (and nnz(B) == 0 alpha*A).
+ *   Aliasing: the inputs are only read, so A and B may be the same arrays; a C array overlapping
+ *     an input is undefined.
+ *   Timing: the structure kernels (k_geam_mark, k_geam_count) under SPG_PHASE_SYMBOLIC, the two
+ *     scans under SPG_PHASE_SCAN, the value kernel (k_geam_fill) under SPG_PHASE_NUMERIC. */
+spg_status_t spg_csrgeam_nnz(spg_handle_t handle, const spg_csr_t *A, const spg_csr_t *B,
+                             void *C_indptr, spg_index_t C_indptr_type, int64_t *nnzC,
+                             size_t *workspace_bytes, void *workspace);
+spg_status_t spg_csrgeam(spg_handle_t handle, const void *alpha, const spg_csr_t *A,
+                         const void *beta, const spg_csr_t *B, spg_csr_t *C,
+                         size_t workspace_bytes, void *workspace);
+
 /* ALG1 single pass: after spg_symbolic, C's column indices and values may already sit
  * compact in the workspace (nnzC entries at *indices / *values; NULL otherwise).  A
  * caller may hand exactly these pointers to spg_numeric as C->indices / C->values: the
@@ -360,10 +413,11 @@ spg_status_t spg_cols16_join(spg_handle_t handle, spg_csr_t *M, const uint32_t *
 typedef enum {
     SPG_PHASE_PRODUCTS = 0,   /* k_row_products: P_i per row                      */
     SPG_PHASE_SCAN = 1,       /* k_scan_lb / k_items_to_rowptr: prefix sums       */
-    SPG_PHASE_SYMBOLIC = 2,   /* k_row (count) / k_tile_sym(_seg) / k_symbolic     */
+    SPG_PHASE_SYMBOLIC = 2,   /* k_row (count) / k_tile_sym(_seg) / k_symbolic;    */
+                              /* spg_csrgeam_nnz's k_geam_mark / k_geam_count      */
     SPG_PHASE_NUMERIC = 3,    /* k_row / k_tile_dn / k_tile_sp / k_tile /          */
                               /* k_numeric: values (ALG1 also structure); one       */
-                              /* kernel per launch                                  */
+                              /* kernel per launch; spg_csrgeam's k_geam_fill       */
     SPG_PHASE_COMPACT = 4,    /* k_compact: ALG1 copy into C                        */
     SPG_PHASE_VALIDATE = 5,   /* k_validate                                         */
     SPG_PHASE_SPILL = 6,      /* k_symbolic / k_numeric over the rows the short-row */

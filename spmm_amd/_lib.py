@@ -47,7 +47,8 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_numeric", "spg_peak_bytes", "spg_validate_csr", "spg_plan_destroy",
            "spg_set_timing", "spg_get_timing", "spg_result_in_workspace", "spg_spmv",
            "spg_spgemm_ws", "spg_plan_info", "spg_tile_value_offsets", "spg_tile_values",
-           "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm", "spg_csr2csc")
+           "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm", "spg_csr2csc",
+           "spg_csrgeam_nnz", "spg_csrgeam")
 
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
@@ -123,6 +124,9 @@ def load():
             "spg_spmv": (ctypes.c_int, [vp, csrp, vp, vp, vp, vp]),
             "spg_spmm": (ctypes.c_int, [vp, csrp, dnp, vp, vp, dnp]),
             "spg_csr2csc": (ctypes.c_int, [vp, csrp, csrp, ctypes.POINTER(sz), vp]),
+            "spg_csrgeam_nnz": (ctypes.c_int, [vp, csrp, csrp, vp, ctypes.c_int, ctypes.POINTER(i64),
+                                               ctypes.POINTER(sz), vp]),
+            "spg_csrgeam": (ctypes.c_int, [vp, vp, csrp, vp, csrp, csrp, sz, vp]),
             "spg_symbolic": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(i64)]),
             "spg_numeric": (ctypes.c_int, [vp, vp, vp, csrp]),
             "spg_peak_bytes": (ctypes.c_int, [vp, ctypes.POINTER(sz)]),

@@ -25,6 +25,7 @@
 #include "spgemm_row.hpp"
 #include "spgemm_spmm.hpp"
 #include "spgemm_transpose.hpp"
+#include "spgemm_geam.hpp"
 
 using namespace spg;
 
@@ -2247,6 +2248,151 @@ spg_status_t spg_csr2csc(spg_handle_t h, const spg_csr_t* A, spg_csr_t* AT, size
     }
     char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     return i64 ? tr_run<int64_t>(h, *A, *AT, L, ws) : tr_run<int32_t>(h, *A, *AT, L, ws);
+}
+
+// ----------------------------------------------------------------------------- spg_csrgeam
+extern "C++" {
+namespace {
+
+// Workspace carve of spg_csrgeam_nnz / spg_csrgeam (offsets from the 256-byte aligned base).
+struct GmLayout {
+    int64_t chunksA = 0, chunksB = 0;   // wave chunks of GM_CHUNK entries
+    size_t scalars = 0;                 // 16 int64: [0] a scan's total, [1] its overflow flag
+    size_t status_b = 0, status_r = 0;  // look-back words of the scan over B's entries / over the rows
+    size_t S = 0;                       // nnz(B) + 1 IP: B-only marks, scanned in place (kept for the value pass)
+    size_t cnt = 0;                     // rows + 1 int64: entries per row of C
+    size_t total = 0;                   // bytes to ask for (256 of slack for the base alignment)
+};
+
+GmLayout gm_layout(const spg_csr_t& A, const spg_csr_t& B) {
+    GmLayout L;
+    const size_t ips = A.indptr_type == SPG_INDEX_64I ? 8 : 4;
+    L.chunksA = (A.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    L.chunksB = (B.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    size_t off = 0;
+    L.scalars = off;
+    off += align_up(16 * sizeof(int64_t));
+    L.status_b = off;
+    off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(B.nnz) + 1));
+    L.status_r = off;
+    off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(A.rows) + 1));
+    L.S = off;
+    off += align_up(ips * ((size_t)B.nnz + 1));
+    L.cnt = off;
+    off += align_up(sizeof(int64_t) * ((size_t)A.rows + 1));
+    L.total = off + 256;
+    return L;
+}
+
+// what both entry points ask of the operands
+spg_status_t gm_check(const spg_csr_t* A, const spg_csr_t* B) {
+    if (!A || !B) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = check_csr(A);
+    if (st || (st = check_csr(B))) return st;
+    if (A->rows != B->rows || A->cols != B->cols || A->value_type != B->value_type ||
+        A->indptr_type != B->indptr_type)
+        return SPG_STATUS_INVALID_VALUE;
+    return SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP>
+spg_status_t gm_structure(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, const GmLayout& L, char* ws,
+                          CP* Cp, int64_t* nnzC) {
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    IP* S = (IP*)(ws + L.S);
+    int64_t* cnt = (int64_t*)(ws + L.cnt);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if (B.nnz > 0) {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_mark<IP>, dim3((unsigned)grid_for(L.chunksB, GM_WPB)),
+                     dim3(GM_WPB * WAVE), A.rows, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices,
+                     (const IP*)B.indptr, (const int32_t*)B.indices, S);
+        SPG_LAUNCHED(h);
+    }
+    if ((st = launch_scan<IP, IP>(h, B.nnz, S, S, (unsigned long long*)(ws + L.status_b), scal, true))) return st;
+    const unsigned cgrid = (unsigned)std::min<int64_t>(grid_for(A.rows, 256), 1 << 20);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_count<IP>, dim3(cgrid), dim3(256), A.rows, (const IP*)A.indptr,
+                 (const IP*)B.indptr, (const IP*)S, cnt);
+    SPG_LAUNCHED(h);
+    if ((st = launch_scan<CP, int64_t>(h, A.rows, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
+        return st;
+    int64_t sc[2] = {0, 0};
+    if ((st = read_scalars(h, scal, 2, sc))) return st;
+    *nnzC = sc[0];
+    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP, typename T>
+spg_status_t gm_values(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, spg_csr_t& C, const GmLayout& L,
+                       char* ws, T alpha, T beta) {
+    timed_launch(h, SPG_PHASE_NUMERIC, k_geam_fill<IP, CP, T>,
+                 dim3((unsigned)grid_for(L.chunksA + L.chunksB, GM_WPB)), dim3(GM_WPB * WAVE), A.rows, A.nnz,
+                 L.chunksA, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices, (const T*)A.values,
+                 (const IP*)B.indptr, (const int32_t*)B.indices, (const T*)B.values, (const IP*)(ws + L.S),
+                 (const CP*)C.indptr, (int32_t*)C.indices, (T*)C.values, alpha, beta);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+}  // namespace
+}  // extern "C++"
+
+spg_status_t spg_csrgeam_nnz(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, void* C_indptr,
+                             spg_index_t C_indptr_type, int64_t* nnzC, size_t* workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = gm_check(A, B);
+    if (st) return st;
+    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const GmLayout L = gm_layout(*A, *B);
+    if (!workspace) {   // size query: host arithmetic only
+        *workspace_bytes = L.total;
+        return SPG_STATUS_SUCCESS;
+    }
+    if (*workspace_bytes < L.total || !C_indptr) return SPG_STATUS_INVALID_VALUE;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    const bool c64 = C_indptr_type == SPG_INDEX_64I;
+    if (A->rows == 0) {   // the one entry of an empty row pointer
+        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, c64 ? 8 : 4, h->stream));
+        *nnzC = 0;
+        return SPG_STATUS_SUCCESS;
+    }
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    if (A->indptr_type == SPG_INDEX_64I)
+        return c64 ? gm_structure<int64_t, int64_t>(h, *A, *B, L, ws, (int64_t*)C_indptr, nnzC)
+                   : gm_structure<int64_t, int32_t>(h, *A, *B, L, ws, (int32_t*)C_indptr, nnzC);
+    return c64 ? gm_structure<int32_t, int64_t>(h, *A, *B, L, ws, (int64_t*)C_indptr, nnzC)
+               : gm_structure<int32_t, int32_t>(h, *A, *B, L, ws, (int32_t*)C_indptr, nnzC);
+}
+
+spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, const void* beta,
+                         const spg_csr_t* B, spg_csr_t* C, size_t workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!alpha || !beta || !C || !workspace) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = gm_check(A, B);
+    if (st) return st;
+    if (C->rows != A->rows || C->cols != A->cols || C->value_type != A->value_type || C->nnz < 0)
+        return SPG_STATUS_INVALID_VALUE;
+    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const GmLayout L = gm_layout(*A, *B);
+    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if (A->rows == 0 || C->nnz == 0 || A->nnz + B->nnz == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const bool i64 = A->indptr_type == SPG_INDEX_64I, c64 = C->indptr_type == SPG_INDEX_64I;
+    return dispatch_value(A->value_type, [&](auto tag) {
+        using T = decltype(tag);
+        T al, be;
+        std::memcpy(&al, alpha, sizeof(T));
+        std::memcpy(&be, beta, sizeof(T));
+        if (i64)
+            return c64 ? gm_values<int64_t, int64_t, T>(h, *A, *B, *C, L, ws, al, be)
+                       : gm_values<int64_t, int32_t, T>(h, *A, *B, *C, L, ws, al, be);
+        return c64 ? gm_values<int32_t, int64_t, T>(h, *A, *B, *C, L, ws, al, be)
+                   : gm_values<int32_t, int32_t, T>(h, *A, *B, *C, L, ws, al, be);
+    });
 }
 
 spg_status_t spg_result_in_workspace(spg_plan_t p, void** indices, void** values) {

@@ -58,7 +58,7 @@ def check_availability(name: str) -> bool:
     """True when the named routine can run here (a gfx950 device and the built library).
     Memoized like the reference's ``@_util.memoize()`` check (cusparse.py:169-186)."""
     global _available
-    if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr"):
+    if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr", "csrgeam2", "csrgeam"):
         raise ValueError(f"No available version information specified for {name}")
     if _available is None:
         try:
@@ -608,6 +608,76 @@ def csc2csr(x):
     return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True if x._canonical is True else None)
 
 
+def has_csrgeam() -> bool:
+    """True when the loaded library exports spg_csrgeam (added within 0.2.0: an older
+    development build lacks it, and the containers then keep their torch addition)."""
+    lib = _lib.load()
+    return hasattr(lib, "spg_csrgeam_nnz") and hasattr(lib, "spg_csrgeam")
+
+
+def csrgeam2(a, b, alpha=1, beta=1):
+    """Matrix-matrix addition ``C = alpha * A + beta * B`` -- the drop-in for
+    ``cupyx.cusparse.csrgeam2`` (modify_src/cupy-src/cupyx/cusparse.py:525-591), on
+    ``spg_csrgeam_nnz`` + ``spg_csrgeam``.
+
+    Args:
+        a (csr_matrix): sparse matrix A, canonical format.
+        b (csr_matrix): sparse matrix B, canonical format, A's shape.
+        alpha (scalar): coefficient for A.
+        beta (scalar): coefficient for B.
+
+    Returns:
+        csr_matrix: C, canonical; its structure is the union of the two patterns (an entry that
+        cancels stays as an explicit 0) and its values equal scipy's after dropping exact zeros.
+    """
+    if not check_availability("csrgeam2"):
+        raise RuntimeError("csrgeam2 is not available.")
+    if not isinstance(a, csr_matrix):
+        raise TypeError("unsupported type (actual: {})".format(type(a)))
+    if not isinstance(b, csr_matrix):
+        raise TypeError("unsupported type (actual: {})".format(type(b)))
+    assert a.has_canonical_format
+    assert b.has_canonical_format
+    if a.shape != b.shape:
+        raise ValueError("inconsistent shapes")
+    if a.device.type != "cuda" or b.device != a.device:
+        raise RuntimeError("csrgeam2 needs device-resident operands on one device")
+    m, n = a.shape
+    a, b = _cast_common_type(a, b)
+    dev, dt = a.device, a.data.dtype
+    # nnz(C) <= nnz(A) + nnz(B): int32 row pointers whenever that bound fits, so no retry
+    ipd = torch.int32 if a.nnz + b.nnz <= 2 ** 31 - 1 else torch.int64
+    h = _handle_for(a)
+    ap, bp = a.indptr.to(ipd).contiguous(), b.indptr.to(ipd).contiguous()
+    aj, ax, bj, bx = a.indices.contiguous(), a.data.contiguous(), b.indices.contiguous(), b.data.contiguous()
+    va = SpgCsr(m, n, a.nnz, ap.data_ptr(), aj.data_ptr() if a.nnz else 0, ax.data_ptr() if a.nnz else 0,
+                _IT[ipd], _VT[dt])
+    vb = SpgCsr(m, n, b.nnz, bp.data_ptr(), bj.data_ptr() if b.nnz else 0, bx.data_ptr() if b.nnz else 0,
+                _IT[ipd], _VT[dt])
+    c_indptr = torch.empty(m + 1, dtype=ipd, device=dev)
+    nnz = ctypes.c_int64(0)
+    ws_bytes = ctypes.c_size_t(0)
+    check(h.lib.spg_csrgeam_nnz(h.ptr, ctypes.byref(va), ctypes.byref(vb), None, _IT[ipd], ctypes.byref(nnz),
+                                ctypes.byref(ws_bytes), None), "spg_csrgeam_nnz")
+    # workspace from torch's caching allocator on the current stream, as in _spgemm
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    check(h.lib.spg_csrgeam_nnz(h.ptr, ctypes.byref(va), ctypes.byref(vb), ctypes.c_void_p(c_indptr.data_ptr()),
+                                _IT[ipd], ctypes.byref(nnz), ctypes.byref(ws_bytes),
+                                ctypes.c_void_p(ws.data_ptr())), "spg_csrgeam_nnz")
+    nnzc = int(nnz.value)
+    c_indices = torch.empty(nnzc, dtype=torch.int32, device=dev)
+    c_data = torch.empty(nnzc, dtype=dt, device=dev)
+    vc = SpgCsr(m, n, nnzc, c_indptr.data_ptr(), c_indices.data_ptr() if nnzc else 0,
+                c_data.data_ptr() if nnzc else 0, _IT[ipd], _VT[dt])
+    al, be = _alpha_of(dt, alpha), _alpha_of(dt, beta)
+    check(h.lib.spg_csrgeam(h.ptr, ctypes.byref(al), ctypes.byref(va), ctypes.byref(be), ctypes.byref(vb),
+                            ctypes.byref(vc), ws_bytes, ctypes.c_void_p(ws.data_ptr())), "spg_csrgeam")
+    return csr_matrix._from_parts(c_data, c_indices, c_indptr, (m, n), canonical=True)
+
+
+csrgeam = csrgeam2
+
+
 def num_products(a: csr_matrix, b: csr_matrix) -> int:
     """P = number of scalar products of A.B (cusparseSpGEMM_getNumProducts); GFLOPS = 2P/t."""
     h = _handle_for(a)
@@ -655,5 +725,5 @@ def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float 
         torch.cuda.current_stream(a.device).synchronize()
 
 
-__all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "check_availability", "num_products", "validate_csr", "SpgError",
+__all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "csrgeam2", "csrgeam", "check_availability", "num_products", "validate_csr", "SpgError",
            "last_stats"]

@@ -13,7 +13,11 @@ Mirrors the part of ``cupyx.scipy.sparse`` that the reference's hot path goes th
 * ``csc_matrix`` / ``coo_matrix`` operands of ``@`` are converted to CSR first
   (_csr.py:167-184);
 * ``csr_matrix.tocsc()`` / ``.transpose()`` / ``.T`` (_csr.py:512-533) and
-  ``csc_matrix((data, indices, indptr), shape=...)``.
+  ``csc_matrix((data, indices, indptr), shape=...)``;
+* ``A + B``, ``A - B`` and ``-A`` (``_add``, _compressed.py:321-360; ``_add_sparse``,
+  _csr.py:84-96 and _csc.py:250-262): ``sum_duplicates()`` on both operands, then
+  ``cusparse.csrgeam2`` (``spg_csrgeam``) for device tensors and the torch form of the same
+  rule otherwise; a csc result for csc operands, through the free transposes.
 
 CSR <-> CSC conversion of device tensors runs in libmi355_spgemm.so (``spg_csr2csc``, a stable
 counting sort: scipy's own order, so transposed products stay bit-exact with scipy); COO
@@ -64,8 +68,90 @@ def _stable_by_index(data, indices, indptr, n_major: int, n_minor: int):
             _indptr_from_rows(indices.to(torch.int64), n_minor, ipd))
 
 
+def _engine_adds(t: torch.Tensor) -> bool:
+    """A + B of these tensors runs on spg_csrgeam: they sit on a GPU and the loaded library
+    exports the symbols (otherwise the torch addition serves)."""
+    if t.device.type != "cuda":
+        return False
+    from . import cusparse
+    return cusparse.has_csrgeam()
+
+
+def _negated(x: torch.Tensor) -> torch.Tensor:
+    """-x as a flip of every sign bit (torch's complex negative is 0 - x on some paths, which
+    leaves a +0.0 part at +0.0)."""
+    return torch.view_as_complex(-torch.view_as_real(x)) if x.is_complex() else -x
+
+
+def _scaled(coef, x: torch.Tensor) -> torch.Tensor:
+    """coef == 1 ? x : coef * x with every product and sum rounded on its own.  A complex product
+    is spelled out on the real parts, (ac - bd) + (ad + bc)i: torch's own complex multiply may
+    fuse them."""
+    if coef == 1:
+        return x
+    if not x.is_complex():
+        return x * torch.tensor(float(coef), dtype=x.dtype, device=x.device)
+    c = complex(coef)
+    xr = torch.view_as_real(x)
+    re, im = xr[..., 0], xr[..., 1]
+    cr = torch.tensor(c.real, dtype=re.dtype, device=x.device)
+    ci = torch.tensor(c.imag, dtype=re.dtype, device=x.device)
+    return torch.view_as_complex(torch.stack((cr * re - ci * im, cr * im + ci * re), dim=-1).contiguous())
+
+
+def _geam_torch(a: "csr_matrix", b: "csr_matrix", alpha, beta) -> "csr_matrix":
+    """alpha*A + beta*B of two canonical CSR matrices as torch ops -- spg_csrgeam's rule
+    (include/spgemm.h): the union of the two patterns, va + vb where both have the entry, va + 0 or
+    0 + vb elsewhere, entries that cancel kept; (1, -1) is the subtraction, a + (-b)."""
+    if a.shape != b.shape:
+        raise ValueError("inconsistent shapes")
+    m, n = a.shape
+    dt = _TORCH_OF[np.dtype(np.promote_types(a.dtype, b.dtype))]
+    minus = alpha == 1 and beta == -1   # the subtraction A - B: -b by a sign flip, no product
+    va, vb = _scaled(alpha, a.data.to(dt)), (_negated(b.data.to(dt)) if minus else _scaled(beta, b.data.to(dt)))
+    ka = a._row_ids() * max(n, 1) + a.indices.to(torch.int64)
+    kb = b._row_ids() * max(n, 1) + b.indices.to(torch.int64)
+    keys = torch.unique(torch.cat((ka, kb)))   # sorted: row-major, columns ascending
+    pa, pb = torch.searchsorted(keys, ka), torch.searchsorted(keys, kb)
+    # sums on the real parts: torch's complex add is x + (1+0j) * y, and that complex product
+    # turns an infinite part of y into a NaN in its other part
+    parts = torch.view_as_real if dt.is_complex else (lambda t: t)
+    b_at = parts(torch.zeros(keys.numel(), dtype=dt, device=a.device))   # vb; where B has no entry +0,
+    if minus:                                                            # or -0 for a - 0
+        b_at = -b_at
+    b_at[pb] = parts(vb)
+    out = b_at + torch.zeros_like(b_at)   # B-only: 0 + vb
+    out[pa] = parts(va) + b_at[pa]        # both: va + vb; A-only: va + 0
+    data = torch.view_as_complex(out) if dt.is_complex else out
+    rows = torch.div(keys, max(n, 1), rounding_mode="floor")
+    ipd = torch.int32 if keys.numel() <= INT32_MAX else torch.int64
+    return csr_matrix._from_parts(data, (keys - rows * max(n, 1)).to(torch.int32),
+                                  _indptr_from_rows(rows, m, ipd), (m, n), canonical=True)
+
+
+def isspmatrix(x) -> bool:
+    return isinstance(x, _SparseBase)
+
+
 class _SparseBase:
     ndim = 2
+
+    # ------------------------------------------------------------------ addition
+    # (cupyx _base.py:104-114, :154-155: every format adds through its CSR form)
+    def __add__(self, other):
+        return self.tocsr().__add__(other)
+
+    def __radd__(self, other):
+        return self.tocsr().__radd__(other)
+
+    def __sub__(self, other):
+        return self.tocsr().__sub__(other)
+
+    def __rsub__(self, other):
+        return self.tocsr().__rsub__(other)
+
+    def __neg__(self):
+        return -self.tocsr()
 
     @property
     def shape(self):
@@ -90,7 +176,47 @@ class _SparseBase:
         return self.tocsr().__matmul__(other)
 
 
-class csr_matrix(_SparseBase):
+class _Compressed(_SparseBase):
+    """What csr_matrix and csc_matrix share: the ``+`` / ``-`` dispatch of cupyx
+    _compressed.py:321-360."""
+
+    def _add_sparse(self, other, alpha, beta):
+        raise NotImplementedError
+
+    def _add(self, other, lhs_negative, rhs_negative):
+        if np.isscalar(other):
+            if other == 0:
+                if lhs_negative:
+                    return -self
+                return self.copy()
+            raise NotImplementedError("adding a nonzero scalar to a sparse matrix is not supported")
+        if isspmatrix(other):
+            alpha = -1 if lhs_negative else 1
+            beta = -1 if rhs_negative else 1
+            return self._add_sparse(other, alpha, beta)
+        # (a dense operand: the reference adds self.todense(); there is no device todense here)
+        return NotImplemented
+
+    def __add__(self, other):
+        return self._add(other, False, False)
+
+    def __radd__(self, other):
+        return self._add(other, False, False)
+
+    def __sub__(self, other):
+        return self._add(other, False, True)
+
+    def __rsub__(self, other):
+        return self._add(other, True, False)
+
+    def __neg__(self):
+        """Elementwise negative over the same structure (cupyx _data.py:36-38)."""
+        out = self.copy()
+        out.data = _negated(self.data)
+        return out
+
+
+class csr_matrix(_Compressed):
     """Compressed sparse row matrix on the device.
 
     ``csr_matrix(S)``            from a scipy.sparse matrix (uploaded),
@@ -258,6 +384,17 @@ class csr_matrix(_SparseBase):
             raise ValueError("could not interpret dimensions")
         return NotImplemented
 
+    def _add_sparse(self, other, alpha, beta):
+        """alpha*self + beta*other (cupyx _csr.py:84-96): canonicalise both, then csrgeam2 --
+        spg_csrgeam for device tensors, else the torch form of the same rule."""
+        self.sum_duplicates()
+        other = other.tocsr()
+        other.sum_duplicates()
+        if _engine_adds(self.data) and other.device == self.device:
+            from . import cusparse
+            return cusparse.csrgeam2(self, other, alpha, beta)
+        return _geam_torch(self, other, alpha, beta)
+
     def tocsc(self, copy=False) -> "csc_matrix":
         """The same matrix in CSC, array for array what scipy's ``tocsc()`` gives (every
         column in stored entry order, duplicates kept): spg_csr2csc for device tensors."""
@@ -371,7 +508,7 @@ class coo_matrix(_SparseBase):
                              shape=self._shape)
 
 
-class csc_matrix(_SparseBase):
+class csc_matrix(_Compressed):
     """Compressed-column matrix on the device.
 
     ``csc_matrix(S)``            from a scipy.sparse matrix (uploaded),
@@ -436,6 +573,19 @@ class csc_matrix(_SparseBase):
             out = out.copy()
         out._canonical = self._canonical
         return out
+
+    def copy(self):
+        return csc_matrix((self.data.clone(), self.indices.clone(), self.indptr.clone()), shape=self._shape,
+                          canonical=self._canonical)
+
+    def tocsc(self, copy=False):
+        return self.copy() if copy else self
+
+    def _add_sparse(self, other, alpha, beta):
+        """alpha*self + beta*other as a csc_matrix: the CSR addition of the two free transposes
+        (cupyx _csc.py:250-262)."""
+        other = other.tocsc() if isinstance(other, (csr_matrix, csc_matrix)) else other.tocsr().tocsc()
+        return self.transpose()._add_sparse(other.transpose(), alpha, beta).transpose()
 
     def tocsr(self) -> csr_matrix:
         """The same matrix in CSR: spg_csr2csc for device tensors (a canonical CSC gives a
