@@ -293,6 +293,67 @@ spg_status_t spg_csrgeam(spg_handle_t handle, const void *alpha, const spg_csr_t
                          const void *beta, const spg_csr_t *B, spg_csr_t *C,
                          size_t workspace_bytes, void *workspace);
 
+/* Canonicalisation: C = A with its entries grouped by row, sorted, its duplicates summed and / or
+ * its zeros dropped, from CSR or COO input, in two calls like the addition -- a structure pass that
+ * writes C's row pointer and returns nnz(C), then a value pass into the caller's C.
+ * (cusparseXcsrsort, cusparseXcoosort and cusparseXcoo2csr as called by cupyx.cusparse.csrsort,
+ * coosort and coo2csr, cupy-src/cupyx/cusparse.py:832-867, :908-954, :957-984; cupyx's
+ * sum_duplicates and eliminate_zeros, cupy-src/cupyx/scipy/sparse/_compressed.py:971-991,
+ * _csr.py:288-302, _coo.py:270-287 and :356-400; the reference builds its matrices through them,
+ * others/profiler.py:66-69.  Every A @ B, A + B and transpose of a non-canonical operand starts
+ * here.  Added within 0.2.0: a caller detects it by symbol lookup.)
+ *   Input: coo_rows == NULL: A is CSR; its rows may be unsorted and may hold duplicates; a row's
+ *     entries are those between its row pointers.  coo_rows != NULL: A is COO, A->nnz triplets
+ *     (coo_rows[e], A->indices[e], A->values[e]) in any order; A->indptr is ignored and may be
+ *     NULL, and A->indptr_type only names the width of the entry positions used internally
+ *     (SPG_INDEX_32I needs nnz < 2^31).  Indices must lie in range (not checked).  rows and cols
+ *     above 2^31 - 1: SPG_STATUS_NOT_SUPPORTED.  C has A's shape and value type; its row pointer
+ *     may be int32 or int64 whatever A's indptr_type is.
+ *   ops, a sum of spg_canon_op_t:
+ *     COO input is always grouped by row, stably: with ops == 0 C is scipy's coo_tocsr array for
+ *     array, every row in stored order, duplicates kept.  ops == 0 with CSR input is
+ *     SPG_STATUS_INVALID_VALUE (nothing to do).
+ *     SPG_CANON_SORT: a stable sort of the entries by (row, column) -- columns ascend inside a
+ *     row, equal columns stay in stored order; duplicates kept, nnzC == nnz.
+ *     SPG_CANON_SUM (implies SORT): each run of equal (row, column) becomes one entry: the run's
+ *     first value copied bit for bit, the later values added to it one by one in stored order,
+ *     every add separately rounded, complex values part by part -- scipy's csr_sum_duplicates
+ *     loop.  An entry that is not duplicated keeps its bits (-0.0, a NaN's payload); a computed
+ *     NaN follows the rule above (a NaN where the rule gives one, sign and payload unspecified).
+ *     Sums that cancel stay as explicit zeros.  Identical from run to run.
+ *     SPG_CANON_DROP_ZEROS (applied last): entries whose value == 0 are dropped: +-0, for complex
+ *     both parts zero; denormals and NaN stay.  Alone on CSR input the stored order is kept:
+ *     scipy's eliminate_zeros() array for array.  With SUM the sums that cancelled are dropped.
+ *   spg_canonicalize_nnz, workspace == NULL: size query, *workspace_bytes is set by host
+ *     arithmetic and nothing is launched.  workspace != NULL: *workspace_bytes must be >= the
+ *     queried size; writes C_indptr (A->rows + 1 entries of C_indptr_type) and *nnzC.  With SUM
+ *     or DROP_ZEROS it waits for the device once, for nnzC; otherwise nnzC == nnz and it does not
+ *     wait.  SPG_STATUS_OVERFLOW when nnzC does not fit an int32 C_indptr (*nnzC is still set:
+ *     call again with an int64 array).  A's values are read only with DROP_ZEROS, and must then
+ *     not change between the two calls.
+ *   spg_canonicalize: takes the workspace exactly as spg_canonicalize_nnz left it, for the same
+ *     A, coo_rows and ops; C->indptr is the array that call wrote, C->indices / C->values hold
+ *     C->nnz = nnzC entries.  Stream-ordered; does not wait.
+ *   Neither call allocates device memory: every device scalar lives in the workspace.  No global
+ *     atomic places an entry; no position depends on the order in which anything landed.
+ *   Status: NULL handle SPG_STATUS_NOT_INITIALIZED (checked first).  SPG_STATUS_INVALID_VALUE
+ *     for a NULL A, workspace_bytes or nnzC; a NULL C_indptr with a workspace; an unknown op bit;
+ *     a C_indptr_type that is neither index type; a workspace below the queried size
+ *     (spg_canonicalize: or NULL); a NULL C; a C that is not A's shape and value type or holds
+ *     more than nnz entries; a NULL array that is needed.
+ *   Degenerate sizes: rows == 0, cols == 0 and nnz == 0 succeed and leave an all-zero row pointer.
+ *   Aliasing: A is only read; a C array overlapping A's is undefined.
+ *   Timing: the sort (k_tr_hist, k_cn_scatter) under SPG_PHASE_LAYOUT, the scans under
+ *     SPG_PHASE_SCAN, the mark and row-pointer kernels (k_cn_mark, k_tr_indptr / k_cn_indptr)
+ *     under SPG_PHASE_SYMBOLIC, the value kernel (k_cn_fill) under SPG_PHASE_NUMERIC. */
+typedef enum { SPG_CANON_SORT = 1, SPG_CANON_SUM = 2, SPG_CANON_DROP_ZEROS = 4 } spg_canon_op_t;
+
+spg_status_t spg_canonicalize_nnz(spg_handle_t handle, const spg_csr_t *A, const int32_t *coo_rows,
+                                  unsigned ops, void *C_indptr, spg_index_t C_indptr_type,
+                                  int64_t *nnzC, size_t *workspace_bytes, void *workspace);
+spg_status_t spg_canonicalize(spg_handle_t handle, const spg_csr_t *A, const int32_t *coo_rows,
+                              unsigned ops, spg_csr_t *C, size_t workspace_bytes, void *workspace);
+
 /* ALG1 single pass: after spg_symbolic, C's column indices and values may already sit
  * compact in the workspace (nnzC entries at *indices / *values; NULL otherwise).  A
  * caller may hand exactly these pointers to spg_numeric as C->indices / C->values: the

@@ -29,6 +29,7 @@ SPG_C_32F = 4
 SPG_C_64F = 5
 SPG_ALG_DEFAULT, SPG_ALG1, SPG_ALG2, SPG_ALG3 = 0, 1, 2, 3
 SPG_ORDER_COL, SPG_ORDER_ROW = 1, 2
+SPG_CANON_SORT, SPG_CANON_SUM, SPG_CANON_DROP_ZEROS = 1, 2, 4
 
 STATUS_NAMES = {
     0: "SPG_STATUS_SUCCESS", 1: "SPG_STATUS_NOT_INITIALIZED", 2: "SPG_STATUS_ALLOC_FAILED",
@@ -48,7 +49,7 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_set_timing", "spg_get_timing", "spg_result_in_workspace", "spg_spmv",
            "spg_spgemm_ws", "spg_plan_info", "spg_tile_value_offsets", "spg_tile_values",
            "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm", "spg_csr2csc",
-           "spg_csrgeam_nnz", "spg_csrgeam")
+           "spg_csrgeam_nnz", "spg_csrgeam", "spg_canonicalize_nnz", "spg_canonicalize")
 
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
@@ -127,6 +128,9 @@ def load():
             "spg_csrgeam_nnz": (ctypes.c_int, [vp, csrp, csrp, vp, ctypes.c_int, ctypes.POINTER(i64),
                                                ctypes.POINTER(sz), vp]),
             "spg_csrgeam": (ctypes.c_int, [vp, vp, csrp, vp, csrp, csrp, sz, vp]),
+            "spg_canonicalize_nnz": (ctypes.c_int, [vp, csrp, vp, ctypes.c_uint, vp, ctypes.c_int,
+                                                    ctypes.POINTER(i64), ctypes.POINTER(sz), vp]),
+            "spg_canonicalize": (ctypes.c_int, [vp, csrp, vp, ctypes.c_uint, csrp, sz, vp]),
             "spg_symbolic": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(i64)]),
             "spg_numeric": (ctypes.c_int, [vp, vp, vp, csrp]),
             "spg_peak_bytes": (ctypes.c_int, [vp, ctypes.POINTER(sz)]),

@@ -26,6 +26,7 @@
 #include "spgemm_spmm.hpp"
 #include "spgemm_transpose.hpp"
 #include "spgemm_geam.hpp"
+#include "spgemm_canon.hpp"
 
 using namespace spg;
 
@@ -2172,7 +2173,7 @@ spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrL
     for (int p = 0; p < L.passes; ++p) {
         const int shift = 8 * p;
         const bool first = p == 0, last = p == L.passes - 1;
-        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP>, grid, block, nnz, chunks, kin, shift, table);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP>, grid, block, nnz, chunks, TrKeys{kin}, shift, table);
         SPG_LAUNCHED(h);
         if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
         char* out = last ? nullptr : ws + L.buf[p & 1];
@@ -2214,7 +2215,8 @@ spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrL
     }
     // (kin: the sorted columns the last pass left)
     const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP>, dim3(pgrid), dim3(256), nnz, A.cols, kin, ATp);
+    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP, IP>, dim3(pgrid), dim3(256), nnz, A.cols, TrKeys{kin}, ATp,
+                 (const IP*)nullptr);
     SPG_LAUNCHED(h);
     return SPG_STATUS_SUCCESS;
 }
@@ -2392,6 +2394,255 @@ spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, 
                        : gm_values<int64_t, int32_t, T>(h, *A, *B, *C, L, ws, al, be);
         return c64 ? gm_values<int32_t, int64_t, T>(h, *A, *B, *C, L, ws, al, be)
                    : gm_values<int32_t, int32_t, T>(h, *A, *B, *C, L, ws, al, be);
+    });
+}
+
+// ----------------------------------------------------------------------------- spg_canonicalize
+extern "C++" {
+namespace {
+
+// bits of an index below `extent`: the bits of extent - 1 (at least one)
+inline int index_bits(int64_t extent) {
+    int b = 1;
+    while (b < 63 && ((int64_t)1 << b) < extent) ++b;
+    return b;
+}
+
+// Workspace carve of spg_canonicalize_nnz / spg_canonicalize (offsets from the 256-byte aligned
+// base).  The sorted records stay in buf[passes & 1] and the scanned marks in `kept` for the
+// value call.
+struct CnLayout {
+    bool sum = false, drop = false;
+    bool marks = false;         // SUM or DROP_ZEROS: kept[] exists
+    int cbits = 1, rbits = 1;   // key = row << cbits | column
+    bool k64 = false;           // the key takes 64 bits
+    int shift0 = 0;             // the first digit's shift: 0, or cbits when only the rows are sorted (COO, no op)
+    int passes = 0;             // 0: CSR input with DROP_ZEROS alone, no sort (the entries are their own records)
+    int64_t chunks = 0;         // wave chunks of TR_CHUNK entries
+    size_t scalars = 0;         // 16 int64: [0] a scan's total
+    size_t status_t = 0, status_k = 0;   // look-back words of the table scans / of the scan over kept[]
+    size_t table = 0;           // 256 * chunks + 1 IP: a pass's digit histogram, scanned in place
+    size_t kept = 0;            // nnz + 1 IP: the kept marks, scanned in place
+    size_t buf[2] = {0, 0};     // ping-pong record buffers (k_cn_pack writes buf[0])
+    size_t total = 0;           // bytes to ask for (256 of slack for the base alignment)
+};
+
+CnLayout cn_layout(const spg_csr_t& A, bool coo, unsigned ops) {
+    CnLayout L;
+    const size_t ips = A.indptr_type == SPG_INDEX_64I ? 8 : 4;
+    const size_t nnz = (size_t)A.nnz;
+    L.sum = (ops & SPG_CANON_SUM) != 0;
+    L.drop = (ops & SPG_CANON_DROP_ZEROS) != 0;
+    L.marks = L.sum || L.drop;
+    const bool sort = L.sum || (ops & SPG_CANON_SORT) != 0;
+    L.cbits = index_bits(A.cols);
+    L.rbits = index_bits(A.rows);
+    L.k64 = L.cbits + L.rbits > 32;
+    L.shift0 = sort ? 0 : L.cbits;
+    L.passes = sort || coo ? (L.cbits + L.rbits - L.shift0 + 7) / 8 : 0;
+    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
+    size_t off = 0;
+    L.scalars = off;
+    off += align_up(16 * sizeof(int64_t));
+    if (L.passes) {
+        L.status_t = off;
+        off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(TR_RADIX * L.chunks) + 1));
+        L.table = off;
+        off += align_up(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
+    }
+    if (L.marks) {
+        L.status_k = off;
+        off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(A.nnz) + 1));
+        L.kept = off;
+        off += align_up(ips * (nnz + 1));
+    }
+    const size_t rec = align_up((ips == 4 && !L.k64 ? 8 : 16) * nnz);   // sizeof(CnRec<IP, K>)
+    for (int b = 0; b < (L.passes ? 2 : 0); ++b) {
+        L.buf[b] = off;
+        off += rec;
+    }
+    L.total = off + 256;
+    return L;
+}
+
+// what both entry points ask of the input
+spg_status_t cn_check(const spg_csr_t* A, const int32_t* coo_rows, unsigned ops) {
+    if (!A) return SPG_STATUS_INVALID_VALUE;
+    if (A->rows < 0 || A->cols < 0 || A->nnz < 0) return SPG_STATUS_INVALID_VALUE;
+    if (A->cols > 2147483647LL || A->rows > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;   // int32 ids
+    if (A->indptr_type != SPG_INDEX_32I && A->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    if (A->value_type != SPG_R_32F && A->value_type != SPG_R_64F && A->value_type != SPG_C_32F &&
+        A->value_type != SPG_C_64F)
+        return SPG_STATUS_NOT_SUPPORTED;
+    if (A->indptr_type == SPG_INDEX_32I && A->nnz > 2147483647LL) return SPG_STATUS_INVALID_VALUE;
+    if (ops & ~(unsigned)(SPG_CANON_SORT | SPG_CANON_SUM | SPG_CANON_DROP_ZEROS)) return SPG_STATUS_INVALID_VALUE;
+    if (!coo_rows && (!A->indptr || ops == 0)) return SPG_STATUS_INVALID_VALUE;   // CSR: something to do
+    if (A->nnz > 0 && (!A->indices || !A->values)) return SPG_STATUS_INVALID_VALUE;
+    if (A->nnz > 0 && (A->rows == 0 || A->cols == 0)) return SPG_STATUS_INVALID_VALUE;
+    return SPG_STATUS_SUCCESS;
+}
+
+// the sorted records the structure call left (nullptr: unsorted, A's entries themselves)
+template <typename IP, typename K>
+const CnRec<IP, K>* cn_records(const CnLayout& L, char* ws) {
+    return L.passes ? (const CnRec<IP, K>*)(ws + L.buf[L.passes & 1]) : nullptr;
+}
+
+template <typename IP, typename K>
+spg_status_t cn_sort(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows, const CnLayout& L, char* ws) {
+    using Rec = CnRec<IP, K>;
+    static_assert(sizeof(Rec) == (sizeof(IP) + sizeof(K) == 8 ? 8 : 16), "cn_layout's record size");
+    const int64_t nnz = A.nnz, chunks = L.chunks;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    unsigned long long* status = (unsigned long long*)(ws + L.status_t);
+    IP* table = (IP*)(ws + L.table);
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    auto pack = coo_rows ? k_cn_pack<IP, K, CN_FROM_COO> : k_cn_pack<IP, K, CN_FROM_CSR>;
+    timed_launch(h, SPG_PHASE_LAYOUT, pack, grid, block, nnz, chunks, L.cbits, (const int32_t*)A.indices, coo_rows,
+                 (const IP*)A.indptr, A.rows, (Rec*)(ws + L.buf[0]));
+    SPG_LAUNCHED(h);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = L.shift0 + 8 * p;
+        const Rec* in = (const Rec*)(ws + L.buf[p & 1]);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP, CnKeys<IP, K>>, grid, block, nnz, chunks,
+                     CnKeys<IP, K>{in, 0}, shift, table);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
+        timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<IP, K>, grid, block, nnz, chunks, shift, in,
+                     (const IP*)table, (Rec*)(ws + L.buf[(p + 1) & 1]));
+        SPG_LAUNCHED(h);
+    }
+    return SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP, typename K>
+spg_status_t cn_structure(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows, const CnLayout& L, char* ws,
+                          CP* Cp, int64_t* nnzC) {
+    const int64_t nnz = A.nnz;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if (L.passes && (st = cn_sort<IP, K>(h, A, coo_rows, L, ws))) return st;
+    const CnRec<IP, K>* rec = cn_records<IP, K>(L, ws);
+    IP* kept = L.marks ? (IP*)(ws + L.kept) : nullptr;
+    if (L.marks) {
+        const dim3 grid((unsigned)grid_for(nnz, CN_BLOCK)), block(CN_BLOCK);
+        if (!L.drop) {   // (no value is read)
+            timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_mark<IP, K, uint32_t, true, false>, grid, block, nnz, rec,
+                         (const uint32_t*)nullptr, kept);
+        } else {
+            st = dispatch_value(A.value_type, [&](auto tag) {
+                using T = decltype(tag);
+                auto mark = L.sum ? k_cn_mark<IP, K, T, true, true> : k_cn_mark<IP, K, T, false, true>;
+                timed_launch(h, SPG_PHASE_SYMBOLIC, mark, grid, block, nnz, rec, (const T*)A.values, kept);
+                return SPG_STATUS_SUCCESS;
+            });
+            if (st) return st;
+        }
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<IP, IP>(h, nnz, kept, kept, (unsigned long long*)(ws + L.status_k), scal, true)))
+            return st;
+    }
+    if (L.passes) {   // off the sorted keys' rows
+        const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.rows + 1, 256), 1 << 20);
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_tr_indptr<IP, CP, CnKeys<IP, K>>, dim3(pgrid), dim3(256), nnz, A.rows,
+                     CnKeys<IP, K>{rec, L.cbits}, Cp, (const IP*)kept);
+    } else {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_indptr<IP, CP>, dim3((unsigned)grid_for(A.rows + 1, CN_BLOCK)),
+                     dim3(CN_BLOCK), A.rows, (const IP*)A.indptr, (const IP*)kept, Cp);
+    }
+    SPG_LAUNCHED(h);
+    *nnzC = nnz;
+    if (L.marks) {
+        int64_t total = 0;
+        if ((st = read_scalars(h, scal, 1, &total))) return st;
+        *nnzC = total;
+    }
+    return (sizeof(CP) == 4 && *nnzC > 2147483647LL) ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename K, typename T, bool SUM>
+spg_status_t cn_values(spg_handle_t h, const spg_csr_t& A, spg_csr_t& C, const CnLayout& L, char* ws) {
+    const K cmask = (K)(((uint64_t)1 << L.cbits) - 1);
+    timed_launch(h, SPG_PHASE_NUMERIC, k_cn_fill<IP, K, T, SUM>, dim3((unsigned)grid_for(A.nnz, CN_BLOCK)),
+                 dim3(CN_BLOCK), A.nnz, cn_records<IP, K>(L, ws), cmask, (const int32_t*)A.indices,
+                 (const T*)A.values, L.marks ? (const IP*)(ws + L.kept) : (const IP*)nullptr, (int32_t*)C.indices,
+                 (T*)C.values);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// f(IP{}, K{}) with the position and key types of this input
+template <typename F>
+spg_status_t cn_dispatch(const spg_csr_t& A, const CnLayout& L, F&& f) {
+    if (A.indptr_type == SPG_INDEX_64I) return L.k64 ? f(int64_t(0), uint64_t(0)) : f(int64_t(0), uint32_t(0));
+    return L.k64 ? f(int32_t(0), uint64_t(0)) : f(int32_t(0), uint32_t(0));
+}
+
+}  // namespace
+}  // extern "C++"
+
+spg_status_t spg_canonicalize_nnz(spg_handle_t h, const spg_csr_t* A, const int32_t* coo_rows, unsigned ops,
+                                  void* C_indptr, spg_index_t C_indptr_type, int64_t* nnzC,
+                                  size_t* workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = cn_check(A, coo_rows, ops);
+    if (st) return st;
+    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const CnLayout L = cn_layout(*A, coo_rows != nullptr, ops);
+    if (!workspace) {   // size query: host arithmetic only
+        *workspace_bytes = L.total;
+        return SPG_STATUS_SUCCESS;
+    }
+    if (*workspace_bytes < L.total || !C_indptr) return SPG_STATUS_INVALID_VALUE;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    const bool c64 = C_indptr_type == SPG_INDEX_64I;
+    if (A->rows == 0 || A->nnz == 0) {   // an all-zero row pointer
+        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, (c64 ? 8 : 4) * (size_t)(A->rows + 1), h->stream));
+        *nnzC = 0;
+        return SPG_STATUS_SUCCESS;
+    }
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    return cn_dispatch(*A, L, [&](auto ip, auto key) {
+        using IP = decltype(ip);
+        using K = decltype(key);
+        return c64 ? cn_structure<IP, int64_t, K>(h, *A, coo_rows, L, ws, (int64_t*)C_indptr, nnzC)
+                   : cn_structure<IP, int32_t, K>(h, *A, coo_rows, L, ws, (int32_t*)C_indptr, nnzC);
+    });
+}
+
+spg_status_t spg_canonicalize(spg_handle_t h, const spg_csr_t* A, const int32_t* coo_rows, unsigned ops,
+                              spg_csr_t* C, size_t workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!C || !workspace) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = cn_check(A, coo_rows, ops);
+    if (st) return st;
+    if (C->rows != A->rows || C->cols != A->cols || C->value_type != A->value_type || C->nnz < 0 ||
+        C->nnz > A->nnz)
+        return SPG_STATUS_INVALID_VALUE;
+    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const CnLayout L = cn_layout(*A, coo_rows != nullptr, ops);
+    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if (!L.marks && C->nnz != A->nnz) return SPG_STATUS_INVALID_VALUE;   // nothing is dropped: nnzC == nnz
+    if (C->nnz == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    return cn_dispatch(*A, L, [&](auto ip, auto key) {
+        using IP = decltype(ip);
+        using K = decltype(key);
+        if (L.sum)
+            return dispatch_value(A->value_type, [&](auto tag) {
+                return cn_values<IP, K, decltype(tag), true>(h, *A, *C, L, ws);
+            });
+        switch (vbytes(A->value_type)) {   // values are moved as raw bits of their width
+            case 4: return cn_values<IP, K, TrBits<4>::type, false>(h, *A, *C, L, ws);
+            case 8: return cn_values<IP, K, TrBits<8>::type, false>(h, *A, *C, L, ws);
+            default: return cn_values<IP, K, TrBits<16>::type, false>(h, *A, *C, L, ws);
+        }
     });
 }
 

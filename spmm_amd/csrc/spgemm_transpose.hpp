@@ -52,6 +52,15 @@ template <> struct TrBits<8> { using type = uint64_t; };
 template <> struct TrBits<16> { using type = TrBits16; };
 
 __device__ __forceinline__ int tr_digit(int32_t key, int shift) { return (int)(((uint32_t)key >> shift) & 255u); }
+__device__ __forceinline__ int tr_digit(uint32_t key, int shift) { return (int)((key >> shift) & 255u); }
+__device__ __forceinline__ int tr_digit(uint64_t key, int shift) { return (int)((key >> shift) & 255u); }
+
+// Where a pass's keys come from: a plain array of column indices (spg_csr2csc); the sort records
+// of spg_canonicalize are another (CnKeys).  KS(e) is entry e's key.
+struct TrKeys {
+    const int32_t* keys;
+    __device__ __forceinline__ uint32_t operator()(int64_t e) const { return (uint32_t)keys[e]; }
+};
 
 // The row of entry e: the last r in [lo, hi] with Ap[r] <= e (Ap[lo] <= e; empty rows skipped).
 template <typename IP>
@@ -65,9 +74,8 @@ __device__ __forceinline__ int64_t tr_row_of(const IP* __restrict__ Ap, int64_t 
 }
 
 // Digit histogram of every chunk into table[digit * chunks + chunk].
-template <typename IP>
-__global__ __launch_bounds__(TR_WPB * WAVE) void k_tr_hist(int64_t nnz, int64_t chunks,
-                                                          const int32_t* __restrict__ keys, int shift,
+template <typename IP, typename KS = TrKeys>
+__global__ __launch_bounds__(TR_WPB * WAVE) void k_tr_hist(int64_t nnz, int64_t chunks, KS keys, int shift,
                                                           IP* __restrict__ table) {
     __shared__ uint32_t hist_s[TR_WPB][TR_RADIX];
     const int l = lane_id();
@@ -78,9 +86,29 @@ __global__ __launch_bounds__(TR_WPB * WAVE) void k_tr_hist(int64_t nnz, int64_t 
     for (int d = l; d < TR_RADIX; d += WAVE) hist[d] = 0;
     wsync();
     const int64_t e0 = chunk * TR_CHUNK, e1 = min(nnz, e0 + TR_CHUNK);
-    for (int64_t e = e0 + l; e < e1; e += WAVE) atomicAdd(&hist[tr_digit(keys[e], shift)], 1u);
+    for (int64_t e = e0 + l; e < e1; e += WAVE) atomicAdd(&hist[tr_digit(keys(e), shift)], 1u);
     wsync();
     for (int d = l; d < TR_RADIX; d += WAVE) table[(int64_t)d * chunks + chunk] = (IP)hist[d];
+}
+
+// The ballot-rank placement of one batch of 64 records (every lane of the wave calls it): the
+// output position of this lane's record with digit d -- the wave's LDS cursor of that digit plus
+// the lane's rank among the active lanes with the same digit -- and the cursor moved past them.
+template <typename IP>
+__device__ __forceinline__ int64_t tr_place(bool active, int d, IP* cur) {
+    unsigned long long peers = __ballot(active);   // active lanes with this lane's digit
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1;
+        const unsigned long long m = __ballot(active && bit);
+        peers &= bit ? m : ~m;
+    }
+    const int rank = lane_rank(peers);
+    const IP base = active ? cur[d] : (IP)0;
+    wsync();
+    if (active && rank == 0) cur[d] = base + (IP)__popcll(peers);
+    wsync();
+    return (int64_t)base + rank;
 }
 
 // One pass's scatter.  table: the scanned histogram.  FIRST: records come from A (kin = A's
@@ -126,21 +154,8 @@ __global__ __launch_bounds__(TR_WPB * WAVE) void k_tr_scatter(int64_t nnz, int64
                 pos = pin[e];
             }
         }
-        const int d = tr_digit(key, shift);
-        unsigned long long peers = __ballot(active);   // active lanes with this lane's digit
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const bool bit = (d >> b) & 1;
-            const unsigned long long m = __ballot(active && bit);
-            peers &= bit ? m : ~m;
-        }
-        const int rank = lane_rank(peers);
-        const IP base = active ? cur[d] : (IP)0;
-        wsync();
-        if (active && rank == 0) cur[d] = base + (IP)__popcll(peers);
-        wsync();
+        const int64_t o = tr_place(active, tr_digit(key, shift), cur);
         if (active) {
-            const int64_t o = (int64_t)base + rank;
             if (LAST) {
                 kout[o] = key;
                 ATj[o] = row;
@@ -156,17 +171,19 @@ __global__ __launch_bounds__(TR_WPB * WAVE) void k_tr_scatter(int64_t nnz, int64
 
 // AT's row pointer from the sorted columns: indptr[c] = the number of entries whose column is
 // below c, for every c in [0, cols] (columns compare as the unsigned numbers the digits sorted).
-template <typename IP>
-__global__ __launch_bounds__(256) void k_tr_indptr(int64_t nnz, int64_t cols, const int32_t* __restrict__ skeys,
-                                                 IP* __restrict__ ATp) {
+// With `kept` (spg_canonicalize_nnz: the exclusive prefix of the kept marks over the sorted
+// entries) the count is of kept entries only, kept[that number].
+template <typename IP, typename OUT = IP, typename KS = TrKeys>
+__global__ __launch_bounds__(256) void k_tr_indptr(int64_t nnz, int64_t cols, KS skeys,
+                                                 OUT* __restrict__ ATp, const IP* __restrict__ kept) {
     for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c <= cols; c += (int64_t)gridDim.x * 256) {
         int64_t lo = 0, hi = nnz;   // the first entry with a column >= c
         while (lo < hi) {
             const int64_t mid = (lo + hi) >> 1;
-            if ((int64_t)(uint32_t)skeys[mid] < c) lo = mid + 1;
+            if ((int64_t)skeys(mid) < c) lo = mid + 1;
             else hi = mid;
         }
-        ATp[c] = (IP)lo;
+        ATp[c] = (OUT)(kept ? (int64_t)kept[lo] : lo);
     }
 }
 

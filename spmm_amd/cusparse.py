@@ -58,7 +58,8 @@ def check_availability(name: str) -> bool:
     """True when the named routine can run here (a gfx950 device and the built library).
     Memoized like the reference's ``@_util.memoize()`` check (cusparse.py:169-186)."""
     global _available
-    if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr", "csrgeam2", "csrgeam"):
+    if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr", "csrgeam2", "csrgeam",
+                    "canonicalize", "csrsort"):
         raise ValueError(f"No available version information specified for {name}")
     if _available is None:
         try:
@@ -678,6 +679,102 @@ def csrgeam2(a, b, alpha=1, beta=1):
 csrgeam = csrgeam2
 
 
+def has_canonicalize() -> bool:
+    """True when the loaded library exports spg_canonicalize (added within 0.2.0: an older
+    development build lacks it, and the containers then keep their torch canonicalisation)."""
+    lib = _lib.load()
+    return hasattr(lib, "spg_canonicalize_nnz") and hasattr(lib, "spg_canonicalize")
+
+
+def _canonicalize_arrays(data, indices, indptr, coo_rows, shape, ops: int, indptr_dtype=None):
+    """(data, indices, indptr) of the m x n matrix after ``ops`` (a sum of the SPG_CANON_* bits),
+    on spg_canonicalize_nnz + spg_canonicalize.  The input is CSR (``coo_rows`` None) or COO
+    (``coo_rows`` the int32 row of every entry, ``indptr`` None).  The row pointer comes back as
+    ``indptr_dtype``, by default int32 whenever the stored entries fit."""
+    dev, dt = data.device, data.dtype
+    m, n = int(shape[0]), int(shape[1])
+    nnz = int(data.numel())
+    ipd = torch.int32 if nnz <= 2 ** 31 - 1 else torch.int64
+    cpd = indptr_dtype or ipd
+    if nnz == 0:
+        return (torch.empty(0, dtype=dt, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.zeros(m + 1, dtype=cpd, device=dev))
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _lib.get_handle(idx)
+    h.set_stream(_current_stream_ptr(idx))
+    data, indices = data.contiguous(), indices.to(torch.int32).contiguous()
+    if coo_rows is not None:
+        coo_rows = coo_rows.to(torch.int32).contiguous()
+    else:
+        indptr = indptr.to(ipd).contiguous()
+    va = SpgCsr(m, n, nnz, 0 if coo_rows is not None else indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
+                _IT[ipd], _VT[dt])
+    rows_p = ctypes.c_void_p(coo_rows.data_ptr()) if coo_rows is not None else None
+    c_indptr = torch.empty(m + 1, dtype=cpd, device=dev)
+    nnzc = ctypes.c_int64(0)
+    ws_bytes = ctypes.c_size_t(0)
+    check(h.lib.spg_canonicalize_nnz(h.ptr, ctypes.byref(va), rows_p, ops, None, _IT[cpd], ctypes.byref(nnzc),
+                                     ctypes.byref(ws_bytes), None), "spg_canonicalize_nnz")
+    # workspace from torch's caching allocator on the current stream, as in _spgemm
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    check(h.lib.spg_canonicalize_nnz(h.ptr, ctypes.byref(va), rows_p, ops, ctypes.c_void_p(c_indptr.data_ptr()),
+                                     _IT[cpd], ctypes.byref(nnzc), ctypes.byref(ws_bytes),
+                                     ctypes.c_void_p(ws.data_ptr())), "spg_canonicalize_nnz")
+    nc = int(nnzc.value)
+    c_indices = torch.empty(nc, dtype=torch.int32, device=dev)
+    c_data = torch.empty(nc, dtype=dt, device=dev)
+    vc = SpgCsr(m, n, nc, c_indptr.data_ptr(), c_indices.data_ptr() if nc else 0, c_data.data_ptr() if nc else 0,
+                _IT[cpd], _VT[dt])
+    check(h.lib.spg_canonicalize(h.ptr, ctypes.byref(va), rows_p, ops, ctypes.byref(vc), ws_bytes,
+                                 ctypes.c_void_p(ws.data_ptr())), "spg_canonicalize")
+    return c_data, c_indices, c_indptr
+
+
+def canonicalize(x, sort=True, sum_duplicates=True, eliminate_zeros=False):
+    """A new ``csr_matrix`` from a ``csr_matrix`` or ``coo_matrix``: its entries grouped by row
+    (COO input, always), sorted by column inside each row, stably (``sort``), duplicates summed
+    one by one in stored order (``sum_duplicates``, implies ``sort``) and exact zeros dropped
+    afterwards (``eliminate_zeros``) -- what cupyx spreads over ``csrsort`` / ``coosort`` /
+    ``coo2csr`` (modify_src/cupy-src/cupyx/cusparse.py:832-984), ``sum_duplicates`` and
+    ``eliminate_zeros``, in one pass over ``spg_canonicalize_nnz`` + ``spg_canonicalize``.  The
+    result is flagged canonical when duplicates were summed."""
+    from .sparse import coo_matrix
+    if not check_availability("canonicalize"):
+        raise RuntimeError("canonicalize is not available.")
+    if not isinstance(x, (csr_matrix, coo_matrix)):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError("canonicalize needs device-resident operands")
+    ops = ((_lib.SPG_CANON_SORT if sort else 0) | (_lib.SPG_CANON_SUM if sum_duplicates else 0) |
+           (_lib.SPG_CANON_DROP_ZEROS if eliminate_zeros else 0))
+    if isinstance(x, coo_matrix):
+        parts = _canonicalize_arrays(x.data, x.col, None, x.row, x.shape, ops)
+        was = None
+    elif ops == 0:   # a CSR matrix with nothing to do
+        return x.copy()
+    else:
+        parts = _canonicalize_arrays(x.data, x.indices, x.indptr, None, x.shape, ops)
+        was = x._canonical
+    return csr_matrix._from_parts(*parts, x.shape, canonical=True if sum_duplicates or was is True else None)
+
+
+def csrsort(x):
+    """Sorts the indices of every row of ``x`` in place, stably, duplicates kept -- the drop-in
+    for ``cupyx.cusparse.csrsort`` (modify_src/cupy-src/cupyx/cusparse.py:832-867), on
+    ``spg_canonicalize`` with SPG_CANON_SORT."""
+    if not check_availability("csrsort"):
+        raise RuntimeError("csrsort is not available.")
+    if not isinstance(x, csr_matrix):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError("csrsort needs device-resident operands")
+    if x._canonical is True:
+        return
+    x.data, x.indices, _ = _canonicalize_arrays(x.data, x.indices, x.indptr, None, x.shape, _lib.SPG_CANON_SORT,
+                                                x.indptr.dtype)
+    x._canonical = None   # sorted now; canonical when it holds no duplicates
+
+
 def num_products(a: csr_matrix, b: csr_matrix) -> int:
     """P = number of scalar products of A.B (cusparseSpGEMM_getNumProducts); GFLOPS = 2P/t."""
     h = _handle_for(a)
@@ -725,5 +822,6 @@ def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float 
         torch.cuda.current_stream(a.device).synchronize()
 
 
-__all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "csrgeam2", "csrgeam", "check_availability", "num_products", "validate_csr", "SpgError",
+__all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "csrgeam2", "csrgeam", "canonicalize", "csrsort",
+           "check_availability", "num_products", "validate_csr", "SpgError",
            "last_stats"]

@@ -20,9 +20,11 @@ Mirrors the part of ``cupyx.scipy.sparse`` that the reference's hot path goes th
   rule otherwise; a csc result for csc operands, through the free transposes.
 
 CSR <-> CSC conversion of device tensors runs in libmi355_spgemm.so (``spg_csr2csc``, a stable
-counting sort: scipy's own order, so transposed products stay bit-exact with scipy); COO
-conversion and duplicate summing run as torch device ops, as does CSR <-> CSC for tensors that
-are not on a GPU.  The multiply itself runs only in the library.
+counting sort: scipy's own order, so transposed products stay bit-exact with scipy), and so do
+``sum_duplicates()``, ``eliminate_zeros()`` and ``coo_matrix.tocsr()`` (``spg_canonicalize``: a
+stable sort by (row, column), duplicates added one by one in stored order).  For tensors that are
+not on a GPU all of these run as torch ops with the same results.  The multiply itself runs only
+in the library.
 """
 from __future__ import annotations
 
@@ -75,6 +77,16 @@ def _engine_adds(t: torch.Tensor) -> bool:
         return False
     from . import cusparse
     return cusparse.has_csrgeam()
+
+
+def _engine_canonicalizes(t: torch.Tensor, shape) -> bool:
+    """Sorting, duplicate summing, zero dropping and COO -> CSR of these tensors run on
+    spg_canonicalize: they sit on a GPU, both extents fit the engine's int32 row and column ids
+    and the loaded library exports the symbols (otherwise the torch form of the same rule serves)."""
+    if t.device.type != "cuda" or max(shape) > INT32_MAX:
+        return False
+    from . import cusparse
+    return cusparse.has_canonicalize()
 
 
 def _negated(x: torch.Tensor) -> torch.Tensor:
@@ -308,10 +320,17 @@ class csr_matrix(_Compressed):
 
     def sum_duplicates(self) -> None:
         """Sort indices and add up duplicates in place (cupyx _compressed.py:971-991).
-        Duplicates are added in stored order, sequentially."""
+        Duplicates are added in stored order, sequentially: spg_canonicalize for device
+        tensors, else the torch form of the same rule."""
         if self._canonical is True or (self._canonical is None and self.has_canonical_format):
             return
         m, n = self._shape
+        if _engine_canonicalizes(self.data, self._shape):
+            from . import _lib, cusparse
+            self.data, self.indices, self.indptr = cusparse._canonicalize_arrays(
+                self.data, self.indices, self.indptr, None, self._shape, _lib.SPG_CANON_SUM, self.indptr.dtype)
+            self._canonical = True
+            return
         rows = self._row_ids()
         key = rows * max(n, 1) + self.indices.to(torch.int64)
         key_s, order = torch.sort(key, stable=True)
@@ -331,6 +350,14 @@ class csr_matrix(_Compressed):
         self.sum_duplicates() if self._canonical is not True else None
 
     def eliminate_zeros(self) -> None:
+        """Drop the stored entries that equal zero, in place, the stored order kept (cupyx
+        _csr.py:288-302): spg_canonicalize for device tensors, else the torch form."""
+        if _engine_canonicalizes(self.data, self._shape):
+            from . import _lib, cusparse
+            self.data, self.indices, self.indptr = cusparse._canonicalize_arrays(
+                self.data, self.indices, self.indptr, None, self._shape, _lib.SPG_CANON_DROP_ZEROS,
+                self.indptr.dtype)
+            return
         keep = self.data != 0
         if bool(keep.all()):
             return
@@ -491,7 +518,17 @@ class coo_matrix(_SparseBase):
             self._shape = (int(shape[0]), int(shape[1]))
 
     def tocsr(self) -> csr_matrix:
+        """The same matrix as a canonical CSR matrix, duplicates summed in stored order (cupyx
+        _coo.py tocsr: sum_duplicates, then coo2csr): spg_canonicalize for device tensors, else
+        the torch form of the same rule."""
         m, n = self._shape
+        if _engine_canonicalizes(self.data, self._shape):
+            from . import _lib, cusparse
+            data, indices, indptr = cusparse._canonicalize_arrays(self.data, self.col, None, self.row, self._shape,
+                                                                  _lib.SPG_CANON_SUM)
+            if indptr.dtype == torch.int64 and data.numel() <= INT32_MAX:
+                indptr = indptr.to(torch.int32)
+            return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True)
         key = self.row * max(n, 1) + self.col
         key_s, order = torch.sort(key, stable=True)
         data_s = self.data[order]
@@ -501,6 +538,20 @@ class coo_matrix(_SparseBase):
         ipd = torch.int32 if uniq.numel() <= INT32_MAX else torch.int64
         return csr_matrix((data_u, (uniq - urow * max(n, 1)).to(torch.int32),
                            _indptr_from_rows(urow, m, ipd)), shape=(m, n), canonical=True)
+
+    def sum_duplicates(self) -> None:
+        """Sort the entries by (row, column) and add up duplicates in place, in stored order,
+        sequentially; the matrix stays COO (cupyx _coo.py:356-400).  Through ``tocsr()``: the
+        row ids are read back off the CSR row pointer."""
+        c = self.tocsr()
+        self.data, self.col, self.row = c.data, c.indices.to(torch.int64), c._row_ids()
+
+    def eliminate_zeros(self) -> None:
+        """Drop the stored entries that equal zero, in place, the stored order kept (cupyx
+        _coo.py:270-287).  Three masked copies: grouping the entries by row, which is what the
+        engine's COO input does first, would change the stored order."""
+        keep = self.data != 0
+        self.data, self.row, self.col = self.data[keep].contiguous(), self.row[keep], self.col[keep]
 
     def get(self):
         import scipy.sparse as sp
