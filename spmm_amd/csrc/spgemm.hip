@@ -102,6 +102,7 @@ struct spg_plan_s {
                                     // adjacent tiles' segments of a B row side by side)
     int twss = 10;                  // log2 of the symbolic tile width (>= tws, <= 16)
     bool sym_seg = false;           // symbolic tiles by the segment-walking kernel (long segments)
+    bool sym_flags = false;         // ... marking a byte per column (k_tile_sym_flag) instead of a bitmap
     bool counts_ready = false;      // a symbolic pass has completed (counts / offsets valid)
     unsigned long long* lb = nullptr;   // ALG1 single pass: per-row look-back status words
     void* ext = nullptr;            // ALG1 on k_row: every A entry's B row extent (RowExt)
@@ -634,6 +635,16 @@ inline bool tile_dense(const spg_plan_s& p) {
     const int cap = (p.A.value_type == SPG_R_64F && p.lean) ? DN_TW_MAX : TILE_CAP;   // (k_tile_dn<.., 2048>)
     return p.use_tile && (1 << p.tws) <= cap && tile_variant().dense;
 }
+// The flag-map symbolic kernel (k_tile_sym_flag, spgemm_tile_dn.hpp) measured slower than
+// k_tile_sym_seg on config 4 (2.63 against 2.29 ms), so no plan selects it.  SPG_SYM_FLAGS=1
+// (read per plan: a schedule-only switch for A/B timing and the tests; results are identical)
+// uses it for every tile-path plan with dense numeric tiles, whatever the segment lengths, and
+// without sym_full's shortcut; sparse numeric tiles need the packed bitmap it does not write.
+inline bool want_sym_flags(const spg_plan_s& p) {
+    if (!tile_dense(p)) return false;
+    const char* e = std::getenv("SPG_SYM_FLAGS");
+    return e && std::strcmp(e, "1") == 0;
+}
 inline int64_t tile_item_slots(const spg_plan_s& p) { return tile_dense(p) ? p.A.rows * p.G : tile_items(p); }
 // item counts / offsets of chunk c (dense tiles: every chunk's stay, at its rows' place)
 inline int64_t* tile_chunk_items(const spg_plan_s& p, int64_t c) {
@@ -1019,13 +1030,28 @@ spg_status_t tile_sym_chunk(spg_handle_t h, spg_plan_s& p, int64_t c) {
     const int64_t r0 = tile_chunk_r0(p, c), n = tile_chunk_r1(p, c) - r0;
     int64_t* items = tile_chunk_items(p, c);
     if (n > 0) {
-        if (p.sym_seg)
+        if (p.sym_flags) {
+            constexpr int W = SPG_SYM_FLAG_W;
+            KernelTimer kt(h, SPG_PHASE_SYMBOLIC);
+            hipExtLaunchKernelGGL((k_tile_sym_flag<IP, W>), dim3(coop_grid(n * sym_tiles(p), W)), dim3(W * WAVE),
+                                  (size_t)1 << p.twss, h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, p.twss,
+                                  (const IP*)p.A.indptr, (const int32_t*)p.A.indices, (const IP*)p.B.indptr,
+                                  (const uint16_t*)p.bj16, (const uint32_t*)p.sidx, items);
+        } else if (p.sym_seg) {
+#if SPG_SYM_DIAG
+            timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym_seg<IP, true>, dim3(tile_grid(n * sym_tiles(p), SEG_WPB)),
+                         dim3(SEG_WPB * WAVE), r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr,
+                         (const int32_t*)p.A.indices, (const IP*)p.B.indptr, (const uint16_t*)p.bj16,
+                         (const uint32_t*)p.sidx, tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items,
+                         sym_full(p) ? p.B.cols : (int64_t)0);
+            SPG_LAUNCHED(h);
+#endif
             timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym_seg<IP>, dim3(tile_grid(n * sym_tiles(p), SEG_WPB)),
                          dim3(SEG_WPB * WAVE), r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr,
                          (const int32_t*)p.A.indices, (const IP*)p.B.indptr, (const uint16_t*)p.bj16,
                          (const uint32_t*)p.sidx, tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items,
                          sym_full(p) ? p.B.cols : (int64_t)0);
-        else if (SPG_SYM8 && SPG_SYM8_CW > 1)   // shared bitmap, SPG_SYM8_CW waves per task
+        } else if (SPG_SYM8 && SPG_SYM8_CW > 1)   // shared bitmap, SPG_SYM8_CW waves per task
             timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym8c<IP, SPG_SYM8_CW>,
                          dim3(coop_grid(n * sym_tiles(p), SPG_SYM8_CW)), dim3(SPG_SYM8_CW * WAVE),
                          r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr, (const int32_t*)p.A.indices,
@@ -1652,6 +1678,7 @@ spg_status_t spg_plan(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, sp
         tmp.TR = 1;
         tmp.twss = sym_tile_log2(*B, tmp.tws, &tmp.sym_seg);
         tmp.rgs = record_group_log2(tmp);
+        tmp.sym_flags = want_sym_flags(tmp);
     }
     // the general kernel's launch over the spill list (rows the short kernels hand over: A
     // rows > 64 entries, C wider than 16384 columns, or a row whose repeated columns overflow

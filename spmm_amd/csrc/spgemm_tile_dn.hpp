@@ -780,46 +780,35 @@ constexpr int SEG_WPB = 2;
 #define SPG_SYM_NQ 4   // (A/B: quads of A entries per round of k_tile_sym_seg)
 #endif
 // SPG_SYM_PF (round 6): the first SPG_SYM_PF steps of a k_tile_sym_seg round load together, with
-// the next round's extents loaded under them (config 4 symbolic 2.74 -> 2.51 ms; 0: round 5's loop)
+// the next round's extents loaded under them (config 4 symbolic 2.74 -> 2.51 ms; 0: round 5's loop).
+// 3 steps in flight cost 151 VGPRs = 3 waves per SIMD; 2 steps fit the 128 of 4 waves per SIMD
+// (SPG_SYM_SEG_OCC) without a spill, and 16 waves per CU beat the third step: config 4 symbolic
+// 2.52 -> 2.29 ms (3 steps capped at 128 VGPRs spill, 2.62 ms; 1 step 2.45 ms, or 2.32 ms at 5 waves
+// per SIMD; 2 steps at 5 waves spill, 2.73 ms: profiles/sym_flags.txt)
 #ifndef SPG_SYM_PF
-#define SPG_SYM_PF 3
+#define SPG_SYM_PF 2
 #endif
-// `ncols` > 0 (plans whose C rows are expected to be full, SPG_SYM_FULL in spgemm.hip): every 64
-// A entries the wave counts its bitmap, and a task whose columns [lo, min(lo + width, ncols))
-// are all set stops walking -- later products cannot add a column (config 3 at density 0.1:
-// C rows 100 % dense, ~90 of 819 A entries fill a row).
-template <typename IP>
-__global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
-    int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
-    const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
-    const uint32_t* __restrict__ sidx, uint32_t* __restrict__ bitmap, int64_t* __restrict__ item_cnt,
-    int64_t ncols) {
+#ifndef SPG_SYM_SEG_OCC
+#define SPG_SYM_SEG_OCC 4   // waves per SIMD k_tile_sym_seg's register allocation must allow (0: the compiler's choice)
+#endif
+// SPG_SYM_DIAG (timing only, A/B builds): k_tile_sym_seg<IP, true> -- every load, one of a lane's
+// eight marks per load -- runs before each k_tile_sym_seg launch, which then writes the counts.
+#ifndef SPG_SYM_DIAG
+#define SPG_SYM_DIAG 0
+#endif
+// The walk of one symbolic task (row, symbolic tile gs of Gs) by one wave: rounds of 4 * NQ A
+// entries starting at entry b0, bstep entries apart (a wave alone on its task: b0 = 0, bstep =
+// 4 * NQ; W waves sharing one: wave w takes b0 = 4 * NQ * w, bstep = 4 * NQ * W).  Every column
+// of the task's B segments goes to mark(column mod 65536), in no particular order;
+// stop(b) -> true before the round at entry b ends the walk.
+template <typename IP, bool DIAG = false, typename Mark, typename Stop>
+__device__ __forceinline__ void sym_seg_walk(int l, int64_t a0, int nA, int b0, int bstep, int gs, int Gs,
+                                             const int32_t* __restrict__ Aj, const IP* __restrict__ Bp,
+                                             const uint16_t* __restrict__ Bj16, const uint32_t* __restrict__ sidx,
+                                             Mark&& mark, Stop&& stop) {
     constexpr int NQ = SPG_SYM_NQ;   // quads of A entries per round: 16 entries, 4 loads in flight per lane
-    __shared__ __attribute__((aligned(16))) uint32_t bits_all[SEG_WPB][SYM_NWMAX];
-    const int l = lane_id();
     const int sub = l & 15, grp = l >> 4;
-    const int wv = uniform((int)(threadIdx.x >> 6));
-    uint32_t* bits = bits_all[wv];
-    const int nw = (1 << tws) >> 5;
-    const int R = 1 << (twss - tws);
-    const int Gs = (G + R - 1) / R;
-    const uint32_t tasks = (uint32_t)(nrows * Gs);
-    const uint32_t stride = gridDim.x * SEG_WPB;
-    for (uint32_t task = xcd_block(gridDim.x) * SEG_WPB + wv; task < tasks; task += stride) {
-        const int64_t row = row0 + (int64_t)(task / (uint32_t)Gs);
-        const int gs = (int)(task % (uint32_t)Gs);
-        const int t0 = gs * R, t1 = min(G, t0 + R);
-        const int lo16 = (t0 << tws) & 0xffff;   // the tile's start inside its 65536-column block
-        const int nws = (t1 - t0) * nw;
-        const int64_t a0 = Ap[row];
-        const int nA = (int)(Ap[row + 1] - a0);
-        if (nA <= 0) {
-            for (int t = t0 + l; t < t1; t += WAVE) item_cnt[(row - row0) * G + t] = 0;
-            continue;
-        }
-        wsync();
-        for (int w = l; w < nws; w += WAVE) bits[w] = 0u;
-        wsync();
+    {
         // NQ quads of entries (4 per quad, one per 16-lane group) per round; the next round's
         // segment extents (A column -> B row start -> symbolic-tile start) are loaded while
         // this round's columns are in flight
@@ -846,9 +835,7 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
         };
         int cnt[NQ];
         int64_t beg[NQ];
-        extents(0, cnt, beg);
-        // the task's valid columns (the last tile of a row may pass the matrix's last column)
-        const int full = ncols > 0 ? (int)min((int64_t)nws * 32, ncols - ((int64_t)t0 << tws)) : 0;
+        extents(b0, cnt, beg);
         // one round: NQ quads of A entries; eight 16-bit columns per lane per 16-byte load, each
         // segment from its 8-aligned start (span = cnt + (beg & 7) elements; an element before
         // beg or past the segment is skipped; the region is padded, so the last load stays
@@ -862,10 +849,10 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
                 const int x = e + 8 * sub;
                 const uint32_t ww[4] = {w[q].x, w[q].y, w[q].z, w[q].w};
 #pragma unroll
-                for (int h = 0; h < 8; ++h) {
+                for (int h0 = 0; h0 < (DIAG ? 1 : 8); ++h0) {
+                    const int h = DIAG ? (l & 7) : h0;   // (DIAG: a lane-dependent one, so the load stays 16 bytes)
                     const int xh = x + h;
-                    if (xh >= odd[q] && xh < span[q])
-                        set_bit(bits, (int)((ww[h >> 1] >> (16 * (h & 1))) & 0xffffu) - lo16);
+                    if (xh >= odd[q] && xh < span[q]) mark((int)((ww[h >> 1] >> (16 * (h & 1))) & 0xffffu));
                 }
             }
         };
@@ -875,14 +862,8 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
             IP xr0[NQ], xr1[NQ];       // (SPG_SYM_PF: the next round's B row starts / ends,
             uint32_t xs0[NQ], xs1[NQ];  // or its symbolic-tile bounds, as loaded)
             bool pend = false;
-            for (int b = 0; b < nA; b += 4 * NQ) {
-                if (full > 0 && b > 0 && (b & (WAVE - 1)) == 0) {   // every 64 entries: full yet?
-                    wsync();
-                    int c = 0;
-                    for (int w = l; w < nws; w += WAVE) c += __popc(bits[w]);
-                    c = wave_incl_sum_dpp(c);
-                    if (readlane_i(c, WAVE - 1) >= full) break;
-                }
+            for (int b = b0; b < nA; b += bstep) {
+                if (stop(b)) break;
                 if (SPG_SYM_PF > 0 && pend) {   // this round's extents from the raw words loaded last round
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) {
@@ -916,7 +897,7 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
                     // round trip per round instead of one per step plus a dependent chain per quad
                     int32_t kn[NQ];
 #pragma unroll
-                    for (int q = 0; q < NQ; ++q) kn[q] = Aj[a0 + min(b + 4 * NQ + 4 * q + grp, nA - 1)];
+                    for (int q = 0; q < NQ; ++q) kn[q] = Aj[a0 + min(b + bstep + 4 * q + grp, nA - 1)];
                     uint4 w[SPG_SYM_PF > 0 ? SPG_SYM_PF : 1][NQ];
 #pragma unroll
                     for (int st = 0; st < SPG_SYM_PF; ++st)
@@ -951,14 +932,69 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
                         const int x = e + 8 * sub;
                         w[q] = x < span[q] ? w0[q][x >> 3] : make_uint4(0u, 0u, 0u, 0u);
                     }
-                    if (SPG_SYM_PF == 0 && e == 0) extents(b + 4 * NQ, cnt, beg);   // (next round; span/odd/w0 are kept)
+                    if (SPG_SYM_PF == 0 && e == 0) extents(b + bstep, cnt, beg);   // (next round; span/odd/w0 are kept)
                     or_step(e, w);
                 }
-                if (SPG_SYM_PF == 0 && mx == 0) extents(b + 4 * NQ, cnt, beg);
+                if (SPG_SYM_PF == 0 && mx == 0) extents(b + bstep, cnt, beg);
             }
         };
         if (Gs == 1) rounds(std::true_type{});
         else rounds(std::false_type{});
+    }
+}
+
+// One wave per task, the task's columns OR-ed into a bitmap in LDS.
+// `ncols` > 0 (plans whose C rows are expected to be full, SPG_SYM_FULL in spgemm.hip): every 64
+// A entries the wave counts its bitmap, and a task whose columns [lo, min(lo + width, ncols))
+// are all set stops walking -- later products cannot add a column (config 3 at density 0.1:
+// C rows 100 % dense, ~90 of 819 A entries fill a row).
+#if SPG_SYM_SEG_OCC > 0
+#define SPG_SYM_SEG_ATTR __attribute__((amdgpu_waves_per_eu(SPG_SYM_SEG_OCC)))
+#else
+#define SPG_SYM_SEG_ATTR
+#endif
+template <typename IP, bool DIAG = false>
+__global__ __launch_bounds__(SEG_WPB * WAVE) SPG_SYM_SEG_ATTR void k_tile_sym_seg(
+    int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
+    const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
+    const uint32_t* __restrict__ sidx, uint32_t* __restrict__ bitmap, int64_t* __restrict__ item_cnt,
+    int64_t ncols) {
+    __shared__ __attribute__((aligned(16))) uint32_t bits_all[SEG_WPB][SYM_NWMAX];
+    const int l = lane_id();
+    const int wv = uniform((int)(threadIdx.x >> 6));
+    uint32_t* bits = bits_all[wv];
+    const int nw = (1 << tws) >> 5;
+    const int R = 1 << (twss - tws);
+    const int Gs = (G + R - 1) / R;
+    const uint32_t tasks = (uint32_t)(nrows * Gs);
+    const uint32_t stride = gridDim.x * SEG_WPB;
+    for (uint32_t task = xcd_block(gridDim.x) * SEG_WPB + wv; task < tasks; task += stride) {
+        const int64_t row = row0 + (int64_t)(task / (uint32_t)Gs);
+        const int gs = (int)(task % (uint32_t)Gs);
+        const int t0 = gs * R, t1 = min(G, t0 + R);
+        const int lo16 = (t0 << tws) & 0xffff;   // the tile's start inside its 65536-column block
+        const int nws = (t1 - t0) * nw;
+        const int64_t a0 = Ap[row];
+        const int nA = (int)(Ap[row + 1] - a0);
+        if (nA <= 0) {
+            for (int t = t0 + l; t < t1; t += WAVE) item_cnt[(row - row0) * G + t] = 0;
+            continue;
+        }
+        wsync();
+        for (int w = l; w < nws; w += WAVE) bits[w] = 0u;
+        wsync();
+        // the task's valid columns (the last tile of a row may pass the matrix's last column)
+        const int full = ncols > 0 ? (int)min((int64_t)nws * 32, ncols - ((int64_t)t0 << tws)) : 0;
+        sym_seg_walk<IP, DIAG>(
+            l, a0, nA, 0, 4 * SPG_SYM_NQ, gs, Gs, Aj, Bp, Bj16, sidx, [&](int c16) { set_bit(bits, c16 - lo16); },
+            [&](int b) {
+                if (full <= 0 || b == 0 || (b & (WAVE - 1)) != 0) return false;   // every 64 entries: full yet?
+                wsync();
+                int c = 0;
+                for (int w = l; w < nws; w += WAVE) c += __popc(bits[w]);
+                c = wave_incl_sum_dpp(c);
+                return readlane_i(c, WAVE - 1) >= full;
+            });
         wsync();
         if (bitmap) {
             uint32_t* __restrict__ out = bitmap + ((row - row0) * G + t0) * (int64_t)nw;
@@ -968,6 +1004,75 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) void k_tile_sym_seg(
             int c = 0;
             for (int q = 0; q < nw; ++q) c += __popc(bits[t * nw + ((q + t) & (nw - 1))]);
             item_cnt[(row - row0) * G + t0 + t] = c;
+        }
+    }
+}
+
+// Symbolic pass for dense numeric tiles (no bitmap output) with the task's columns marked in a
+// byte-per-column flag map instead of a bitmap: a plain ds_write_b8 of the same value from every
+// writer, which needs neither an atomic nor an order, in place of k_tile_sym_seg's ds_or_b32.
+// Measured on config 4 it is NOT faster, so no plan selects it: it runs only under
+// SPG_SYM_FLAGS=1 (spgemm.hip), bit-exact, as the record of the experiment.  At random addresses
+// the LDS is busy the same number of cycles either way (SQ_LDS_IDX_ACTIVE 8.87e8 against 8.52e8,
+// SQ_LDS_BANK_CONFLICT 5.66e8 against 5.69e8: bank conflicts set the cost, not the atomic), the
+// 64 KB map holds a CU to two blocks, and clearing and counting it is extra: 2.63 ms against
+// k_tile_sym_seg's 2.29 ms at the same 16 waves per CU (profiles/sym_flags.txt).
+// One block of W waves per task (row, symbolic tile), as k_tile_sym8c: the map (dynamic shared
+// memory, 1 << twss bytes: 64 KB for a 65536-column tile, two blocks per CU) is cleared with
+// 16-byte stores by all waves; wave w walks rounds w, w + W, ... (sym_seg_walk); then wave w
+// counts the numeric tiles t = w, w + W, ... of the task, 16 flag bytes per lane and read (the
+// flags are 0 or 1, so a word's popcount is its sum).
+#ifndef SPG_SYM_FLAG_W
+#define SPG_SYM_FLAG_W 8   // waves per block (config 4: 2 6.34, 4 3.69, 6 5.29, 8 2.63-3.32 ms, profiles/sym_flags.txt)
+#endif
+#ifndef SPG_SYM_FLAG_OCC
+#define SPG_SYM_FLAG_OCC 4   // waves per SIMD the register allocation must allow: two 8-wave blocks per CU
+#endif
+#if SPG_SYM_FLAG_OCC > 0
+#define SPG_SYM_FLAG_ATTR __attribute__((amdgpu_waves_per_eu(SPG_SYM_FLAG_OCC)))
+#else
+#define SPG_SYM_FLAG_ATTR
+#endif
+template <typename IP, int W>
+__global__ __launch_bounds__(W * WAVE) SPG_SYM_FLAG_ATTR void k_tile_sym_flag(
+    int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
+    const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
+    const uint32_t* __restrict__ sidx, int64_t* __restrict__ item_cnt) {
+    constexpr int NT = W * WAVE;
+    extern __shared__ __attribute__((aligned(16))) uint4 sym_flag_map[];
+    uint8_t* flags = reinterpret_cast<uint8_t*>(sym_flag_map);
+    const int l = lane_id();
+    const int tid = (int)threadIdx.x;
+    const int wv = uniform(tid >> 6);
+    const int R = 1 << (twss - tws);
+    const int Gs = (G + R - 1) / R;
+    const int tw16 = (1 << tws) >> 4;          // 16-byte words of a numeric tile's flags
+    const uint32_t tasks = (uint32_t)(nrows * Gs);
+    for (uint32_t task = xcd_block(gridDim.x); task < tasks; task += gridDim.x) {
+        __syncthreads();   // (the previous task's flags have been counted)
+        const int64_t row = row0 + (int64_t)(task / (uint32_t)Gs);
+        const int gs = (int)(task % (uint32_t)Gs);
+        const int t0 = gs * R, t1 = min(G, t0 + R);
+        const int lo16 = (t0 << tws) & 0xffff;   // the tile's start inside its 65536-column block
+        const int64_t a0 = Ap[row];
+        const int nA = (int)(Ap[row + 1] - a0);
+        if (nA <= 0) {
+            for (int t = t0 + tid; t < t1; t += NT) item_cnt[(row - row0) * G + t] = 0;
+            continue;
+        }
+        for (int q = tid; q < (t1 - t0) * tw16; q += NT) sym_flag_map[q] = make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+        sym_seg_walk<IP>(l, a0, nA, 4 * SPG_SYM_NQ * wv, 4 * SPG_SYM_NQ * W, gs, Gs, Aj, Bp, Bj16, sidx,
+                         [&](int c16) { flags[c16 - lo16] = (uint8_t)1; }, [](int) { return false; });
+        __syncthreads();
+        for (int t = wv; t < t1 - t0; t += W) {
+            int c = 0;
+            for (int q = l; q < tw16; q += WAVE) {
+                const uint4 f = sym_flag_map[t * tw16 + q];
+                c += __popc(f.x) + __popc(f.y) + __popc(f.z) + __popc(f.w);
+            }
+            c = wave_incl_sum_dpp(c);
+            if (l == WAVE - 1) item_cnt[(row - row0) * G + t0 + t] = c;
         }
     }
 }
