@@ -97,7 +97,6 @@ struct spg_plan_s {
     bool lean32 = true;             // fp32 dense tiles may use the entry-run kernel (k_tile_dn<float>)
     int tws = 10;                   // log2 of the tile width
     int G = 1;                      // tiles per row
-    int TR = 1;                     // tiles per wave task (a run of one row's tiles)
     int rgs = 0;                    // log2 of the tiles per record group (tile-major B's layout: RG
                                     // adjacent tiles' segments of a B row side by side)
     int twss = 10;                  // log2 of the symbolic tile width (>= tws, <= 16)
@@ -145,7 +144,7 @@ inline size_t vbytes(spg_dtype_t t) {
 
 // bytes of one tile-major B record of the tile path (column in tile + value, unpadded)
 inline size_t brec_bytes(spg_dtype_t t) {
-    return (SPG_REC10 && t == SPG_R_64F) ? 10 : (SPG_REC6 && t == SPG_R_32F) ? 6 : 4 + vbytes(t);
+    return t == SPG_R_64F ? 10 : t == SPG_R_32F ? 6 : 4 + vbytes(t);   // (rec_bytes, spgemm_tile.hpp)
 }
 
 // Runs f(T{}) with T the C++ type of value type t.
@@ -175,47 +174,6 @@ inline bool row_kernel_enabled() {
     return on;
 }
 
-// Tile numeric kernel variant (A/B timing builds only: `make HIPFLAGS+=-DSPG_TILE_RU=2` etc.;
-// no environment variable can change what the shipped library computes).
-//   SPG_TILE_RU     chunks per owner-round group (1, 2, or all in flight)
-//   SPG_TILE_DENSE  0 turns the column-addressed accumulator off
-//   SPG_TILE_TWS    log2 of a forced tile width (8..12; 0 = the planner's choice)
-// The timing-only diagnostics (SPG_TILE_DIAG, results wrong) exist only in spgemm_tile.hpp
-// builds that define it.
-#ifndef SPG_TILE_RU
-#define SPG_TILE_RU 1
-#endif
-#ifndef SPG_TILE_DENSE
-#define SPG_TILE_DENSE 1
-#endif
-#ifndef SPG_TILE_TWS
-#define SPG_TILE_TWS 0
-#endif
-//   SPG_TILE_LEAN   0 keeps the owner-round k_tile on dense tiles (A/B against k_tile_dn)
-//   SPG_SYM8        symbolic tiles by the word-flattened walk (k_tile_sym8, default) instead of
-//                   k_tile_sym (config 5: 20.1 -> 12.1 ms)
-#ifndef SPG_SYM8
-#define SPG_SYM8 1
-#endif
-//   SPG_SYM8_CW     waves per k_tile_sym8 task sharing one bitmap (1: k_tile_sym8, one wave per task)
-#ifndef SPG_SYM8_CW
-#define SPG_SYM8_CW 2
-#endif
-#ifndef SPG_TILE_LEAN
-#define SPG_TILE_LEAN 1
-#endif
-//   SPG_SP_LEAN     0 keeps the owner-round k_tile on sparse tiles (A/B against k_tile_sp)
-#ifndef SPG_SP_LEAN
-#define SPG_SP_LEAN 1
-#endif
-
-
-struct TileVariant { int ru; bool dense; };
-inline const TileVariant& tile_variant() {
-    static const TileVariant v{SPG_TILE_RU, SPG_TILE_DENSE != 0};
-    return v;
-}
-
 inline int64_t grid_for(int64_t rows, int per_block) { return (rows + per_block - 1) / per_block; }
 
 inline int64_t scan_tiles(int64_t n) { return n > 0 ? (n + SCAN_TILE - 1) / SCAN_TILE : 1; }
@@ -235,8 +193,8 @@ inline bool want_short(const spg_csr_t& A, const spg_csr_t& B) {
 // Wide rows go to the tile path when their C rows are dense enough that a tile of up to
 // 4096 columns holds a useful number of entries.  The tile width keeps the expected
 // entries of a tile within TILE_CAP (or is at most TILE_CAP, which bounds them).
-// `lean`: the fp64 ordered-LDS kernels (k_tile_dn / k_tile_sp) may run -- the build allows them
-// and the handle's run-time check found the LDS ordering they rely on (spg_create)
+// `lean`: the fp64 ordered-LDS kernels (k_tile_dn / k_tile_sp) may run -- the
+// handle's run-time check found the LDS ordering they rely on (spg_create)
 inline bool want_tile(const spg_csr_t& A, const spg_csr_t& B, int& tws, int& G, bool lean) {
     if (A.rows == 0 || B.rows == 0 || B.cols == 0 || A.nnz == 0 || B.nnz == 0) return false;
     const double avgA = (double)A.nnz / (double)A.rows;
@@ -251,15 +209,13 @@ inline bool want_tile(const spg_csr_t& A, const spg_csr_t& B, int& tws, int& G, 
     // fp64 C rows at least half dense and wide: dense tiles of 2048 columns (a 2048-slot
     // accumulator).  Half the items, half the segment-table lookups per product; config 4
     // measured 24.9 against 26.6 ms per product with 1024-column tiles.
-    if (B.value_type == SPG_R_64F && lean && tws == 10 && frac >= 0.5 && B.cols >= 16384) tws = SPG_DN_WIDE_TWS;
+    if (B.value_type == SPG_R_64F && lean && tws == 10 && frac >= 0.5 && B.cols >= 16384) tws = 11;
     // fp64 C rows 10-24 % dense over >= 16384 columns: sparse tiles of 8192 columns (2048-slot
     // windows; half the items, A-row reads and segment-table lookups of 4096-column tiles;
     // config 5: 149.3 -> 124.8 ms per product)
-    if (B.value_type == SPG_R_64F && lean && SPG_SP_LEAN && tws == 12 && frac >= 0.1 &&
+    if (B.value_type == SPG_R_64F && lean && tws == 12 && frac >= 0.1 &&
         B.cols >= 16384 && frac * 8192.0 <= 0.95 * 2048)
-        tws = 13;
-    // (A/B timing builds only; at most 8192 columns: k_tile_sp<.., 2048> holds 256 bitmap words)
-    if (SPG_TILE_TWS >= 8 && SPG_TILE_TWS <= 13) tws = SPG_TILE_TWS;
+        tws = 13;   // (at most 8192 columns: k_tile_sp<.., SpCfg2048> holds 256 bitmap words)
     if (frac * (double)(1 << tws) < 64.0) return false;
     // the tile-major B's segment table is int32 and its records are addressed with 32-bit
     // byte offsets
@@ -273,7 +229,7 @@ inline bool want_tile(const spg_csr_t& A, const spg_csr_t& B, int& tws, int& G, 
 // grid of a tile kernel over `tasks` wave tasks: a multiple of 8 (XCD-aware block ids).  The
 // kernels stride over their tasks, so the grid is capped: its work-item count must stay below
 // 2^32 (the dispatch packet's grid size is 32-bit; 33.5M two-wave blocks failed to launch).
-inline unsigned tile_grid(int64_t tasks, int wpb = TILE_WPB) {
+inline unsigned tile_grid(int64_t tasks, int wpb) {
     const int64_t cap = ((int64_t)1 << 31) / ((int64_t)wpb * WAVE);
     const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(grid_for(tasks, wpb), cap));
     return (unsigned)((nb + 7) / 8 * 8);
@@ -290,10 +246,7 @@ inline unsigned coop_grid(int64_t tasks, int wpb) {
 // and at the (pow2-rounded) row width.  When the widest symbolic tile (65536 columns or the
 // whole row) holds segments of >= SEG_MIN entries, that width and the segment-walking
 // symbolic kernel (k_tile_sym_seg) are used instead.
-#ifndef SPG_SEG_MIN
-#define SPG_SEG_MIN 128
-#endif
-constexpr double SEG_MIN = SPG_SEG_MIN;   // (config 5 segments of 65: 25.9 ms against 20.7 for k_tile_sym)
+constexpr double SEG_MIN = 128;   // (config 5 segments of 65: 25.9 ms against 20.7 for a product-flattened walk)
 inline int sym_tile_log2(const spg_csr_t& B, int tws, bool* seg = nullptr) {
     const double avgB = B.rows > 0 ? (double)B.nnz / (double)B.rows : 0.0;
     int tmax = tws;
@@ -303,7 +256,7 @@ inline int sym_tile_log2(const spg_csr_t& B, int tws, bool* seg = nullptr) {
     if (seg_max >= SEG_MIN) return tmax;
     int t = tws;
     while (t < 16 && ((int64_t)1 << t) < B.cols && avgB * (double)((int64_t)1 << t) / (double)B.cols < 64.0) ++t;
-    return std::max(tws, std::min(t, SPG_SYM_MAXLOG));
+    return std::max(tws, std::min(t, SYM_MAXLOG));
 }
 
 
@@ -633,7 +586,7 @@ inline int64_t tile_items(const spg_plan_s& p) { return p.use_tile ? tile_rows_m
 // rows, not one chunk's), so ALG3's numeric phase does not recompute its chunks' counts.
 inline bool tile_dense(const spg_plan_s& p) {
     const int cap = (p.A.value_type == SPG_R_64F && p.lean) ? DN_TW_MAX : TILE_CAP;   // (k_tile_dn<.., 2048>)
-    return p.use_tile && (1 << p.tws) <= cap && tile_variant().dense;
+    return p.use_tile && (1 << p.tws) <= cap;
 }
 // The flag-map symbolic kernel (k_tile_sym_flag, spgemm_tile_dn.hpp) measured slower than
 // k_tile_sym_seg on config 4 (2.63 against 2.29 ms), so no plan selects it.  SPG_SYM_FLAGS=1
@@ -657,51 +610,39 @@ inline int64_t tiles_padded(const spg_plan_s& p) { return rec_groups(p) << p.rgs
 inline int64_t group_words(const spg_plan_s& p) { return (p.B.rows << p.rgs) + 1; }   // one group's table
 inline int64_t bt_entries(const spg_plan_s& p) { return p.use_tile ? rec_groups(p) * group_words(p) : 0; }
 // fp32 dense tiles take k_tile_dn<float, .., 1024> (plain read-add-write per A entry's run of a
-// chunk) when a tile's expected B segment holds >= SPG_F32_RUN_MIN entries: chunks then hold one
+// chunk) when a tile's expected B segment holds >= F32_RUN_MIN entries: chunks then hold one
 // or two entries' runs (config 3 at density 0.1: 102-entry segments); shorter segments put many
 // entries in a chunk and keep k_tile's owner rounds.  SPG_F32_RUNS=0 (read per plan: a
 // schedule-only switch for A/B timing and the tests) keeps k_tile.
-#ifndef SPG_F32_RUN_MIN
-#define SPG_F32_RUN_MIN 48
-#endif
+constexpr double F32_RUN_MIN = 48;
 inline bool fp32_runs(const spg_plan_s& p) {
     if (!p.lean32 || p.A.value_type != SPG_R_32F || p.B.cols <= 0 || p.B.rows <= 0 || (1 << p.tws) > 1024) return false;
     const char* e = std::getenv("SPG_F32_RUNS");
     if (e && std::strcmp(e, "0") == 0) return false;
     const double seg = (double)p.B.nnz / (double)p.B.rows * (double)(1 << p.tws) / (double)p.B.cols;
-    return seg >= SPG_F32_RUN_MIN;
+    return seg >= F32_RUN_MIN;
 }
 // fp64 8192-column sparse tiles (config 5's shape) run in cooperative record groups of
-// 1 << SPG_SP_RGS tiles (k_tile_sp<.., RG>), on a persistent grid of 8 / RG blocks per CU.
+// 1 << SP_RGS tiles (k_tile_sp<.., RG>), on a persistent grid of 8 / RG blocks per CU.
 // Measured on config 5 (round 5, numeric ms per product): RG 1 97.6 (511 GB of fabric reads per
 // launch); RG 4 with one block per item 103 (361 GB: the block's waves idle until its slowest
 // item ends, and a new block needs a whole block's LDS); RG 4 persistent 92.7 (367 GB), RG 8
 // persistent 91.8 (301 GB), RG 2 persistent 101.3; RG 1 persistent 118.5 (one-wave blocks
 // balance best dispatched one item each).  On the final kernels (saddr record loads), alternated
 // on one box: RG 8 89.7-89.8 against RG 4 91.0-91.3 (abtest/r05_call24.sh) -- RG 8, one 8-wave
-// block per CU (159.6 KiB of LDS).  SPG_SP_RGS=0 builds keep RG = 1.
-#ifndef SPG_SP_RGS
-#define SPG_SP_RGS 3
-#endif
+// block per CU (159.6 KiB of LDS).
+constexpr int SP_RGS = 3;
 // (SPG_SP_RECORD_GROUP=1, read per plan: a schedule-only switch to the one-wave kernel over
 // plain tile-major records, for A/B timing and for the tests; results are identical)
-// (SPG_DN_RGS = 1, A/B builds: fp64 2048-column dense tiles in record groups of 2, one per
-// 2-wave block of k_tile_dn<.., RG = 2> on a persistent grid; config 4 numeric 22.4 ms against
-// 19.1 ms for independent items, round 5)
-#ifndef SPG_DN_RGS
-#define SPG_DN_RGS 0
-#endif
-#ifndef SPG_DN_RG_PERSIST
-#define SPG_DN_RG_PERSIST 1
-#endif
+// (fp64 2048-column dense tiles in record groups of 2, one per 2-wave block on a persistent
+// grid, measured config 4 numeric 22.4 ms against 19.1 ms for independent items, round 5:
+// dense tiles keep plain tile-major records)
 inline int record_group_log2(const spg_plan_s& p) {
-    if (SPG_DN_RGS > 0 && p.use_tile && tile_dense(p) && p.lean && p.A.value_type == SPG_R_64F && p.tws == 11)
-        return SPG_DN_RGS;
-    if (!p.use_tile || tile_dense(p) || !p.lean || !SPG_SP_LEAN) return 0;
+    if (!p.use_tile || tile_dense(p) || !p.lean) return 0;
     if (p.A.value_type != SPG_R_64F || p.tws != 13) return 0;
     const char* e = std::getenv("SPG_SP_RECORD_GROUP");
     if (e && std::strcmp(e, "1") == 0) return 0;
-    return SPG_SP_RGS;
+    return SP_RGS;
 }
 
 // ALG1 runs as one fused pass (k_short SHORT_NUMLB) when the short-row kernel takes the shape
@@ -872,7 +813,7 @@ spg_status_t run_symbolic_rows(spg_handle_t h, spg_plan_s& p, int64_t r0, int64_
     } else if (p.use_short && p.nspc > 0) {
         // k_row counts every row (spills by the chunked loop) and lists this chunk's spills
         timed_launch(h, SPG_PHASE_SYMBOLIC, k_row<double, IP, int64_t, ROW_SYM, RowSmall>,
-                           dim3((unsigned)grid_for(n, RowSmall::WPB * row_pair<ROW_SYM>())), dim3(RowSmall::WPB * WAVE),
+                           dim3((unsigned)grid_for(n, RowSmall::WPB)), dim3(RowSmall::WPB * WAVE),
                            r0, n, p.B.cols, Ap, Aj, (const double*)nullptr, Bp, Bj,
                            (const double*)nullptr, (const int64_t*)nullptr, (int32_t*)nullptr, (double*)nullptr,
                            1.0, p.row_cnt, p.spill + r0, (int32_t*)(p.cspill + chunk), (int)ROW_COUNT_ALL,
@@ -885,7 +826,7 @@ spg_status_t run_symbolic_rows(spg_handle_t h, spg_plan_s& p, int64_t r0, int64_
             PhaseTimer pt(h, SPG_PHASE_SYMBOLIC);
             if (p.use_row)
                 hipLaunchKernelGGL((k_row<double, IP, int64_t, ROW_SYM, RowSmall>),
-                                   dim3((unsigned)grid_for(n, RowSmall::WPB * row_pair<ROW_SYM>())), dim3(RowSmall::WPB * WAVE), 0,
+                                   dim3((unsigned)grid_for(n, RowSmall::WPB)), dim3(RowSmall::WPB * WAVE), 0,
                                    h->stream, r0, n, p.B.cols, Ap, Aj, (const double*)nullptr, Bp, Bj,
                                    (const double*)nullptr, (const int64_t*)nullptr, (int32_t*)nullptr,
                                    (double*)nullptr, 1.0, p.row_cnt, l1, cnt, 0, (int64_t)0,
@@ -932,7 +873,7 @@ spg_status_t run_numeric_rows(spg_handle_t h, spg_plan_s& p, int64_t r0, int64_t
     } else if (p.use_short && p.nspc > 0 && !UB) {
         {
             KernelTimer kt(h, SPG_PHASE_NUMERIC);
-            hipExtLaunchKernelGGL((k_row<T, IP, OFF, ROW_NUM, RowSmall>), dim3((unsigned)grid_for(n, RowSmall::WPB * row_pair<ROW_NUM>())),
+            hipExtLaunchKernelGGL((k_row<T, IP, OFF, ROW_NUM, RowSmall>), dim3((unsigned)grid_for(n, RowSmall::WPB)),
                                   dim3(RowSmall::WPB * WAVE), 0, h->stream, kt.a, kt.b, 0, r0, n, p.B.cols, Ap, Aj, Ax,
                                   Bp, Bj, Bx, off, cj, cx, alpha, p.row_cnt, p.spill + r0, (int32_t*)(p.cspill + chunk),
                                   (int)ROW_LISTED, (int64_t)0, (const int64_t*)nullptr,
@@ -952,7 +893,7 @@ spg_status_t run_numeric_rows(spg_handle_t h, spg_plan_s& p, int64_t r0, int64_t
         {
             PhaseTimer pt(h, SPG_PHASE_NUMERIC);
             if (p.use_row && !UB)
-                hipLaunchKernelGGL((k_row<T, IP, OFF, ROW_NUM, RowSmall>), dim3((unsigned)grid_for(n, RowSmall::WPB * row_pair<ROW_NUM>())),
+                hipLaunchKernelGGL((k_row<T, IP, OFF, ROW_NUM, RowSmall>), dim3((unsigned)grid_for(n, RowSmall::WPB)),
                                    dim3(RowSmall::WPB * WAVE), 0, h->stream, r0, n, p.B.cols, Ap, Aj, Ax, Bp, Bj,
                                    Bx, off, cj, cx, alpha, p.row_cnt, l1, cnt, 0, (int64_t)0,
                                    (const int64_t*)nullptr, (unsigned long long*)nullptr, (int64_t)0,
@@ -1031,42 +972,25 @@ spg_status_t tile_sym_chunk(spg_handle_t h, spg_plan_s& p, int64_t c) {
     int64_t* items = tile_chunk_items(p, c);
     if (n > 0) {
         if (p.sym_flags) {
-            constexpr int W = SPG_SYM_FLAG_W;
+            constexpr int W = SYM_FLAG_W;
             KernelTimer kt(h, SPG_PHASE_SYMBOLIC);
             hipExtLaunchKernelGGL((k_tile_sym_flag<IP, W>), dim3(coop_grid(n * sym_tiles(p), W)), dim3(W * WAVE),
                                   (size_t)1 << p.twss, h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, p.twss,
                                   (const IP*)p.A.indptr, (const int32_t*)p.A.indices, (const IP*)p.B.indptr,
                                   (const uint16_t*)p.bj16, (const uint32_t*)p.sidx, items);
         } else if (p.sym_seg) {
-#if SPG_SYM_DIAG
-            timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym_seg<IP, true>, dim3(tile_grid(n * sym_tiles(p), SEG_WPB)),
-                         dim3(SEG_WPB * WAVE), r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr,
-                         (const int32_t*)p.A.indices, (const IP*)p.B.indptr, (const uint16_t*)p.bj16,
-                         (const uint32_t*)p.sidx, tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items,
-                         sym_full(p) ? p.B.cols : (int64_t)0);
-            SPG_LAUNCHED(h);
-#endif
             timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym_seg<IP>, dim3(tile_grid(n * sym_tiles(p), SEG_WPB)),
                          dim3(SEG_WPB * WAVE), r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr,
                          (const int32_t*)p.A.indices, (const IP*)p.B.indptr, (const uint16_t*)p.bj16,
                          (const uint32_t*)p.sidx, tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items,
                          sym_full(p) ? p.B.cols : (int64_t)0);
-        } else if (SPG_SYM8 && SPG_SYM8_CW > 1)   // shared bitmap, SPG_SYM8_CW waves per task
-            timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym8c<IP, SPG_SYM8_CW>,
-                         dim3(coop_grid(n * sym_tiles(p), SPG_SYM8_CW)), dim3(SPG_SYM8_CW * WAVE),
+        } else {   // shared bitmap, SYM8_CW waves per task
+            timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym8c<IP, SYM8_CW>,
+                         dim3(coop_grid(n * sym_tiles(p), SYM8_CW)), dim3(SYM8_CW * WAVE),
                          r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr, (const int32_t*)p.A.indices,
                          (const IP*)p.B.indptr, (const uint16_t*)p.bj16, (const uint32_t*)p.sidx,
                          tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items);
-        else if (SPG_SYM8)
-            timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym8<IP>, dim3(tile_grid(n * sym_tiles(p))), dim3(TILE_WPB * WAVE),
-                         r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr, (const int32_t*)p.A.indices,
-                         (const IP*)p.B.indptr, (const uint16_t*)p.bj16, (const uint32_t*)p.sidx,
-                         tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items);
-        else
-            timed_launch(h, SPG_PHASE_SYMBOLIC, k_tile_sym<IP>, dim3(tile_grid(n * sym_tiles(p))), dim3(TILE_WPB * WAVE),
-                         r0, n, p.tws, p.G, p.twss, (const IP*)p.A.indptr, (const int32_t*)p.A.indices,
-                         (const IP*)p.B.indptr, (const uint16_t*)p.bj16, (const uint32_t*)p.sidx,
-                         tile_dense(p) ? (uint32_t*)nullptr : p.bitmap, items);
+        }
         SPG_LAUNCHED(h);
     }
     const int64_t nch = tile_chunks(p);
@@ -1162,14 +1086,12 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
         uint32_t it_lo = (uint32_t)(g0 * n), it_hi = (uint32_t)(g1 * n);
         int64_t nit = (g1 - g0) * n;
         KernelTimer kt(h, SPG_PHASE_NUMERIC);
-        // dense accumulator when the tile fits one window; round groups (tile_variant())
+        // dense accumulator when the tile fits one window
         const bool dense = tile_dense(p);
-        const int ru = tile_variant().ru;
-        auto launch = [&](auto dn, auto rn) {
+        auto launch = [&](auto dn) {
             constexpr bool DN = decltype(dn)::value;
-            constexpr int RN = decltype(rn)::value;
             constexpr int WPBN = tile_num_wpb<DN>();
-            hipExtLaunchKernelGGL((k_tile<T, IP, DN, RN>), dim3(tile_grid(nit, WPBN)), dim3(WPBN * WAVE), 0,
+            hipExtLaunchKernelGGL((k_tile<T, IP, DN>), dim3(tile_grid(nit, WPBN)), dim3(WPBN * WAVE), 0,
                                   h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, Ap, Aj, Ax, p.B.rows,
                                   (const uint32_t*)p.brec, (const int32_t*)p.tptr,
                                   dense ? (const uint32_t*)nullptr : (const uint32_t*)p.bitmap,
@@ -1187,7 +1109,7 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
             }
         }
         if constexpr (OrderedLdsAdd<T>::value) {
-            if (!dense && p.lean && SPG_SP_LEAN) {   // sparse tiles, ordered LDS adds
+            if (!dense && p.lean) {   // sparse tiles, ordered LDS adds
                 auto sp = [&](auto cfg, auto rgc) {
                     using CF = decltype(cfg);
                     constexpr int RG = decltype(rgc)::value;
@@ -1208,17 +1130,9 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
                 };
                 using One = std::integral_constant<int, 1>;
                 if constexpr (std::is_same<T, double>::value) {
-                    bool done = false;
-                    if constexpr (SPG_SP_RGS > 0) {
-                        if (p.tws > 12 && p.rgs == SPG_SP_RGS) {
-                            sp(SpCfgRG{}, std::integral_constant<int, (1 << SPG_SP_RGS)>{});
-                            done = true;
-                        }
-                    }
-                    if (!done) {
-                        if (p.tws > 12) sp(SpCfg2048{}, One{});
-                        else sp(SpCfg1024{}, One{});
-                    }
+                    if (p.tws > 12 && p.rgs == SP_RGS) sp(SpCfgRG{}, std::integral_constant<int, (1 << SP_RGS)>{});
+                    else if (p.tws > 12) sp(SpCfg2048{}, One{});
+                    else sp(SpCfg1024{}, One{});
                 } else {
                     sp(SpCfg1024{}, One{});
                 }
@@ -1228,19 +1142,6 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
             if (dense && p.lean) {   // ordered LDS adds (spgemm_tile_dn.hpp)
                 auto dn = [&](auto twd) {
                     constexpr int TWD = decltype(twd)::value;
-                    if constexpr (SPG_DN_RGS > 0 && TWD == 2048) {
-                        if (p.rgs == SPG_DN_RGS) {   // record groups of DN_WPB tiles, one per block
-                            const int64_t q0 = g0 >> p.rgs, q1 = (g1 + DN_WPB - 1) >> p.rgs;
-                            const unsigned gd = (unsigned)std::min<int64_t>(coop_grid((q1 - q0) * n, DN_WPB),
-                                                                            SPG_DN_RG_PERSIST ? (int64_t)h->cus * 4 : ((int64_t)1 << 30));
-                            hipExtLaunchKernelGGL((k_tile_dn<T, IP, TWD, DN_WPB>), dim3(gd), dim3(DN_WPB * WAVE),
-                                                  0, h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, Ap, Aj, Ax, p.B.rows,
-                                                  (const uint32_t*)p.brec, (const int32_t*)p.tptr,
-                                                  (const int64_t*)tile_chunk_items(p, c), cj, cx, alpha,
-                                                  sent(sentinel_region(TWD)), (uint32_t)(q0 * n), (uint32_t)(q1 * n), p.rgs);
-                            return;
-                        }
-                    }
                     hipExtLaunchKernelGGL((k_tile_dn<T, IP, TWD>), dim3(tile_grid(nit, DN_WPB)), dim3(DN_WPB * WAVE),
                                           0, h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, Ap, Aj, Ax, p.B.rows,
                                           (const uint32_t*)p.brec, (const int32_t*)p.tptr,
@@ -1248,13 +1149,6 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
                                           sent(sentinel_region(TWD)), it_lo, it_hi, p.rgs);
                 };
                 if constexpr (std::is_same<T, double>::value) {
-                    if constexpr (DN_TW_MAX > 2048) {
-                        if ((1 << p.tws) > 2048) {
-                            dn(std::integral_constant<int, DN_TW_MAX>{});
-                            SPG_LAUNCHED(h);
-                            continue;
-                        }
-                    }
                     if ((1 << p.tws) > 1024) dn(std::integral_constant<int, 2048>{});
                     else dn(std::integral_constant<int, 1024>{});
                 } else {
@@ -1264,17 +1158,8 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
                 continue;
             }
         }
-        constexpr int UF = sizeof(T) > 8 ? 4 : 8;
-        using D1 = std::integral_constant<bool, true>;
-        using D0 = std::integral_constant<bool, false>;
-        using R1 = std::integral_constant<int, 1>;
-        using R2 = std::integral_constant<int, 2>;
-        using RF = std::integral_constant<int, UF>;
-        if (dense) {
-            if (ru == 2) launch(D1{}, R2{}); else if (ru >= UF) launch(D1{}, RF{}); else launch(D1{}, R1{});
-        } else {
-            if (ru == 2) launch(D0{}, R2{}); else if (ru >= UF) launch(D0{}, RF{}); else launch(D0{}, R1{});
-        }
+        if (dense) launch(std::true_type{});
+        else launch(std::false_type{});
         SPG_LAUNCHED(h);
     }
     return SPG_STATUS_SUCCESS;
@@ -1289,8 +1174,8 @@ spg_status_t alg1_fused_run(spg_handle_t h, spg_plan_s& p, void* cp) {
         // no memset of the control block: the count pass zeroes the scan's status words,
         // spills are counted in the handle's counter, which the scan moves into
         // scalars[5] and re-arms
-        const unsigned grid = (unsigned)grid_for(p.A.rows, RowSmall::WPB * row_pair<ROW_LB>());
-        const unsigned grid_sym = (unsigned)grid_for(p.A.rows, RowSmall::WPB * row_pair<ROW_SYM>());
+        const unsigned grid = (unsigned)grid_for(p.A.rows, RowSmall::WPB);
+        const unsigned grid_sym = (unsigned)grid_for(p.A.rows, RowSmall::WPB);
         // the numeric launch's scan words: ticket + tile status, then the group prefixes
         unsigned long long* status = p.scan_status + scan_tiles(p.A.rows) + 1;
         const int64_t nscan = scan_tiles(p.A.rows);
@@ -1671,11 +1556,10 @@ spg_status_t spg_plan(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, sp
     tmp.seg_len = A->nnz;
     tmp.use_short = want_short(*A, *B);
     tmp.use_row = row_kernel_enabled();
-    tmp.lean = SPG_TILE_LEAN && h->lds_ordered;
-    tmp.lean32 = SPG_TILE_LEAN && h->lds_ordered32;
+    tmp.lean = h->lds_ordered;
+    tmp.lean32 = h->lds_ordered32;
     tmp.use_tile = !tmp.use_short && want_tile(*A, *B, tmp.tws, tmp.G, tmp.lean);
     if (tmp.use_tile) {
-        tmp.TR = 1;
         tmp.twss = sym_tile_log2(*B, tmp.tws, &tmp.sym_seg);
         tmp.rgs = record_group_log2(tmp);
         tmp.sym_flags = want_sym_flags(tmp);

@@ -228,7 +228,7 @@ __device__ __forceinline__ int row_front_commit(Lds& S, int l, const RowFront<T,
 // The register path for a row of P (1 <= P <= NC*64) products: bitmap, positions, the
 // flagged-word list and its fix-up.  o.take = false when the list overflows LCAP (the row
 // then goes to the general kernel; o.nnz is still its count).
-template <int NC, bool VALS, bool AVL, typename T, typename IP, typename G, typename Lds, int NCMAX>
+template <int NC, bool VALS, typename T, typename IP, typename G, typename Lds, int NCMAX>
 __device__ __forceinline__ void row_pass(Lds& S, int l, int cnt, int off, int P, const int32_t* __restrict__ Bj,
                                          const T* __restrict__ Bx, RowOut<T, NCMAX>& o) {
     static_assert(NC <= NCMAX, "chunks");
@@ -272,7 +272,7 @@ __device__ __forceinline__ void row_pass(Lds& S, int l, int cnt, int off, int P,
             j = jr1[src[r]];
         }
         idx[r] = t < P ? j.jb0 + (IP)(t - j.joff) : (IP)0;
-        if constexpr (VALS && !AVL) av[r] = j.ja;
+        if constexpr (VALS) av[r] = j.ja;
     }
     // every product of the row in flight at once
     int col[NC];
@@ -282,13 +282,10 @@ __device__ __forceinline__ void row_pass(Lds& S, int l, int cnt, int off, int P,
         T bx[NC];
 #pragma unroll
         for (int r = 0; r < NC; ++r) bx[r] = ld_idx(Bx, idx[r]);
-        // (AVL) A's values from LDS while the gathers are in flight, not held in registers
-        // across them
+        // (A's values stay in registers across the gathers: re-reading them from LDS afterwards
+        // measured 1.5 us slower on config 2's numeric pass)
 #pragma unroll
-        for (int r = 0; r < NC; ++r) {
-            if constexpr (AVL) o.prd[r] = mul_rn(jr1[src[r]].ja, bx[r]);
-            else o.prd[r] = mul_rn(av[r], bx[r]);
-        }
+        for (int r = 0; r < NC; ++r) o.prd[r] = mul_rn(av[r], bx[r]);
     }
 #pragma unroll
     for (int r = 0; r < NC; ++r)
@@ -403,14 +400,14 @@ __device__ __forceinline__ void row_pass(Lds& S, int l, int cnt, int off, int P,
 // P in [1, PREG]: the register path with the smallest chunk count that holds P, then
 // `then(o)` on its result -- inside each case, so the result of one case
 // never meets another's at a join (it would otherwise occupy registers for all five).
-template <bool VALS, bool AVL, typename T, typename IP, typename G, typename Lds, typename F>
+template <bool VALS, typename T, typename IP, typename G, typename Lds, typename F>
 __device__ __forceinline__ void row_dispatch(Lds& S, int l, int cnt, int off, int P, const int32_t* __restrict__ Bj,
                                              const T* __restrict__ Bx, F&& then) {
     static_assert(G::R == 10, "dispatch covers 10 chunks");
     auto run = [&](auto nct) {
         constexpr int NC = decltype(nct)::value;
         RowOut<T, NC> o;
-        row_pass<NC, VALS, AVL, T, IP, G>(S, l, cnt, off, P, Bj, Bx, o);
+        row_pass<NC, VALS, T, IP, G>(S, l, cnt, off, P, Bj, Bx, o);
         then(o);
     };
     switch ((P + WAVE - 1) / WAVE) {   // exact chunk counts where rows are common
@@ -523,22 +520,10 @@ __device__ int row_count_only(Lds& S, int l, int64_t a0, int nA, const int32_t* 
 //     count pass listed them).  cap > 0 (ALG1, C's arrays hold `cap` entries): a row that
 //     would end past cap writes nothing (the host sees the total and redoes the product).
 enum { ROW_COUNT_ALL = 1, ROW_LISTED = 2 };
-#ifndef SPG_ROW_PAIR
-#define SPG_ROW_PAIR 1
-#endif
-#ifndef SPG_ROW_PAIR_SYM
-#define SPG_ROW_PAIR_SYM 1
-#endif
-// rows per wave, per mode.  Two rows per wave in the count pass (42 VGPRs, still 8 waves per
-// SIMD: config 2's 16384 rows become one generation of 8192 resident waves) measured no
-// gain (12.7 vs 12.1 us; three rows 15 us): the count pass is bound by its ~370 VALU
-// instructions per row, not by the dependent-load chain
-template <int MODE> constexpr int row_pair() { return MODE == 0 ? SPG_ROW_PAIR_SYM : SPG_ROW_PAIR; }
-// A's values re-read from LDS after the gathers instead of held in registers across them
-// (ROW_LB only): fewer live registers, but measured 1.5 us slower on config 2's numeric pass
-#ifndef SPG_ROW_AVLDS
-#define SPG_ROW_AVLDS 0
-#endif
+// One row per wave in every mode (RP below).  Two rows per wave in the count pass (42 VGPRs,
+// still 8 waves per SIMD: config 2's 16384 rows become one generation of 8192 resident waves)
+// measured no gain (12.7 vs 12.1 us; three rows 15 us): the count pass is bound by its ~370
+// VALU instructions per row, not by the dependent-load chain
 // register budget: 5 waves per SIMD (<= 96 VGPRs) for 4- and 8-byte values
 template <typename T, typename IP, typename OFF, int MODE, typename G>
 __global__ __launch_bounds__(G::WPB * WAVE, sizeof(T) <= 8 ? 5 : 3) void k_row(
@@ -553,8 +538,10 @@ __global__ __launch_bounds__(G::WPB * WAVE, sizeof(T) <= 8 ? 5 : 3) void k_row(
     static_assert(G::WPB * WAVE == BLOCK, "scan tiles are blocks of BLOCK threads");
     constexpr bool VALS = MODE != ROW_SYM;
     constexpr bool lb = MODE == ROW_LB;
-    constexpr bool AVL = lb && SPG_ROW_AVLDS;
-    constexpr int RP = row_pair<MODE>();
+    // rows per wave.  (The loops over RP below stay as they are: written out for one row, every
+    // k_row instantiation came out with other registers, and this kernel's code is to stay
+    // what was measured.)
+    constexpr int RP = 1;
     __shared__ __attribute__((aligned(16))) RowLds<T, IP, G, VALS> lds[G::WPB];
     // (ALG1 count pass) the next launch's scan status words are zeroed here: no memset
     if (zero_words)
@@ -576,9 +563,8 @@ __global__ __launch_bounds__(G::WPB * WAVE, sizeof(T) <= 8 ? 5 : 3) void k_row(
     const int wv = uniform((int)(threadIdx.x >> 6));
     RowLds<T, IP, G, VALS>& S = lds[wv];
     const bool count_all = MODE == ROW_SYM && (flags & ROW_COUNT_ALL);
-    // ROW_PAIR consecutive rows per wave: both rows' fronts (A entries, B row extents) are
-    // loaded before the first row is worked on, so the second row's dependent loads are
-    // in flight during the first row's gathers and LDS work
+    // RP consecutive rows per wave, every row's front (A entries, B row extents) loaded before
+    // the first row is worked on
     const int64_t it0 = (((int64_t)blockIdx.x - (lb ? sa.nscan : 0)) * G::WPB + wv) * RP;
     if (it0 >= nrows) return;
     const int nr = (int)min((int64_t)RP, nrows - it0);
@@ -642,7 +628,7 @@ __global__ __launch_bounds__(G::WPB * WAVE, sizeof(T) <= 8 ? 5 : 3) void k_row(
         bool take = false;
         int nnz = 0;
         if (fits && P > 0) {
-            row_dispatch<VALS, AVL, T, IP, G>(S, l, f.cnt, off, P, Bj, Bx, [&](const auto& o) {
+            row_dispatch<VALS, T, IP, G>(S, l, f.cnt, off, P, Bj, Bx, [&](const auto& o) {
                 take = o.take;
                 nnz = o.nnz;
                 if (take && lb) {

@@ -31,11 +31,6 @@ constexpr int SPMM_WPB = 4;
 constexpr int SPMM_UNROLL = 8;      // B-row gathers in flight per wave (k_spmm_row)
 constexpr int SPMM_UNROLL_P = 4;    // per lane group (k_spmm_row_packed)
 constexpr int SPMM_CH = 512;        // A entries staged per wave per chunk (k_spmm_col)
-// k_spmm_col task order: 1 = column strip outermost (the waves in flight gather from one strip's
-// NC columns of B, a slab that fits L2), 0 = row group outermost (A/B timing builds only)
-#ifndef SPMM_COL_STRIP_MAJOR
-#define SPMM_COL_STRIP_MAJOR 1
-#endif
 
 // V consecutive values moved as one access (16 bytes when V > 1).
 template <typename T, int V> struct alignas(V == 1 ? alignof(T) : sizeof(T) * V) SpmmVec { T v[V]; };
@@ -220,8 +215,10 @@ __global__ __launch_bounds__(SPMM_WPB * WAVE) void k_spmm_col(int64_t rows, int6
     const int64_t step = (int64_t)gridDim.x * SPMM_WPB;
     for (int64_t t = (int64_t)blockIdx.x * SPMM_WPB + wv; t < tasks; t += step) {
         const int64_t rgs = (rows + WAVE - 1) / WAVE;
-        const int64_t rg = SPMM_COL_STRIP_MAJOR ? t % rgs : t / cstrips;
-        const int64_t cb = (SPMM_COL_STRIP_MAJOR ? t / rgs : t - rg * cstrips) * NC;   // first column
+        // tasks run column strip outermost: the waves in flight gather from one strip's NC columns
+        // of B, a slab that fits L2
+        const int64_t rg = t % rgs;
+        const int64_t cb = t / rgs * NC;   // first column
         const int nc = (int)min((int64_t)NC, n - cb);     // columns of this strip (>= 1)
         const int64_t r0 = rg * WAVE, r1 = min(rows, r0 + WAVE);
         const int64_t row = r0 + l;

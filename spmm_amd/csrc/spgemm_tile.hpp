@@ -15,24 +15,12 @@
 
 namespace spg {
 
-constexpr int TILE_WPB = 2;           // waves per block
 // waves per block of the numeric kernel: sparse tiles (14 KB of LDS per wave) fit 11
 // one-wave blocks per CU where 2-wave blocks fit 10; dense tiles (13 KB) fit 12 either way
 template <bool DENSE> constexpr int tile_num_wpb() { return DENSE ? 2 : 1; }
 constexpr int TILE_CAP = 1024;        // entries per window
 constexpr int TILE_NWMAX = 128;       // bitmap words per tile: TW <= 4096 columns
 constexpr int TILE_MK = 1024;         // marker bytes: 16 chunks of 64 products per group
-
-template <typename T, typename IP, bool VALS> struct TileLds {
-    uint32_t bits[TILE_NWMAX];
-    uint16_t wpre[TILE_NWMAX];
-    T acc[VALS ? TILE_CAP : 1];
-    uint32_t tag[VALS ? TILE_CAP : 1];
-    T ja[WAVE];
-    IP jb0[WAVE];
-    uint32_t joff[WAVE];
-    uint8_t mk[TILE_MK];
-};
 
 // Numeric tile pass LDS: the bitmap word and its popcount prefix side by side (one 8-byte
 // read per product; sparse tiles only), the A-entry table as one 8-byte entry per lane (the
@@ -107,76 +95,49 @@ __global__ __launch_bounds__(256) void k_tile_index(int64_t rows, const IP* __re
 // Offsets are 32-bit byte offsets from the (scalar) base: the host keeps the record array
 // under 4 GiB on the tile path.
 template <typename T> constexpr int rec_words() { return 1 + (int)(sizeof(T) / 4); }
-// SPG_REC10 (round 4, default): fp64 records of 10 bytes -- the value, then the column inside the
-// tile as u16 (tiles
+// fp64 records (round 4) take 10 bytes -- the value, then the column inside the tile as u16 (tiles
 // are at most 8192 columns wide, sentinel columns below 65536) -- packed without padding, so a
 // tile's slice is 5/6 of the 12-byte form (config 4's 2048-column slice 8.0 -> 6.7 MB against an
 // XCD's 4 MB L2).  Record i starts at byte 10i, which is 0 or 2 modulo 4: one dwordx3 load from
 // the dword below it holds the whole record, and two v_alignbit and a shift take it apart.
 // Measured (A/B on one box): config 4 numeric 20.7 -> 19.8 ms, config 5 103.7 -> 98.7 ms.
-#ifndef SPG_REC10
-#define SPG_REC10 1
-#endif
-// SPG_REC6 (round 5, default): fp32 records of 6 bytes the same way -- the value, then the column
+// fp32 records (round 5) take 6 bytes the same way -- the value, then the column
 // inside the tile as u16 (fp32 tiles are at most 4096 columns wide) -- record i at byte 6i (0 or 2
 // modulo 4): one dwordx2 from the dword below it, one v_alignbit.  8 -> 6 bytes per product of
 // gather traffic for the fp32 tile kernels.
-#ifndef SPG_REC6
-#define SPG_REC6 1
-#endif
 template <typename T> constexpr int rec_bytes() {
-    return (SPG_REC10 && std::is_same<T, double>::value) ? 10
-           : (SPG_REC6 && std::is_same<T, float>::value) ? 6 : 4 * rec_words<T>();
+    return std::is_same<T, double>::value ? 10 : std::is_same<T, float>::value ? 6 : 4 * rec_words<T>();
 }
 
-#ifndef SPG_REC_NT
-#define SPG_REC_NT 0   // (A/B: record gathers with the non-temporal policy, bypassing the CU's L1)
-#endif
-typedef unsigned int spg_u32x3 __attribute__((ext_vector_type(3)));
 template <typename T, typename IP>
 __device__ __forceinline__ void load_rec(const uint32_t* __restrict__ rec, IP i, int& lc, T& v) {
-    constexpr int W = rec_words<T>();
     if constexpr (rec_bytes<T>() == 10) {   // fp64, 10-byte records
         const char* p = reinterpret_cast<const char*>(rec) + (uint64_t)((uint32_t)i * 10u);
         const uint32_t sh = (uint32_t)((uintptr_t)p & 2u) * 8u;     // 0 or 16 bits
-        uint3 x;
-        if constexpr (SPG_REC_NT) {
-            const spg_u32x3 y = __builtin_nontemporal_load(reinterpret_cast<const spg_u32x3*>(p - ((uintptr_t)p & 2u)));
-            x = make_uint3(y.x, y.y, y.z);
-        } else {
-            x = *reinterpret_cast<const uint3*>(p - ((uintptr_t)p & 2u));
-        }
+        const uint3 x = *reinterpret_cast<const uint3*>(p - ((uintptr_t)p & 2u));
         const uint32_t lo = __builtin_amdgcn_alignbit(x.y, x.x, sh);
         const uint32_t hi = __builtin_amdgcn_alignbit(x.z, x.y, sh);
         v = __hiloint2double((int)hi, (int)lo);
         lc = (int)((x.z >> sh) & 0xffffu);
-        return;
     } else if constexpr (rec_bytes<T>() == 6) {   // fp32, 6-byte records
         const char* p = reinterpret_cast<const char*>(rec) + (uint64_t)((uint32_t)i * 6u);
         const uint32_t sh = (uint32_t)((uintptr_t)p & 2u) * 8u;
         const uint2 x = *reinterpret_cast<const uint2*>(p - ((uintptr_t)p & 2u));
         v = __uint_as_float(__builtin_amdgcn_alignbit(x.y, x.x, sh));
         lc = (int)((x.y >> sh) & 0xffffu);
-        return;
-    }
-    const uint32_t* __restrict__ q =
-        reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(rec) + (uint64_t)((uint32_t)i * (uint32_t)(4 * W)));
-    if constexpr (W == 2) {          // f32
-        const uint2 x = *reinterpret_cast<const uint2*>(q);
-        v = __uint_as_float(x.x);
-        lc = (int)x.y;
-    } else if constexpr (W == 3) {   // f64, complex64
-        const uint3 x = *reinterpret_cast<const uint3*>(q);
-        if constexpr (std::is_same<T, double>::value) {
-            v = __hiloint2double((int)x.y, (int)x.x);
-        } else {
+    } else {   // complex: value and column in whole words
+        constexpr int W = rec_words<T>();
+        const uint32_t* __restrict__ q = reinterpret_cast<const uint32_t*>(
+            reinterpret_cast<const char*>(rec) + (uint64_t)((uint32_t)i * (uint32_t)(4 * W)));
+        if constexpr (W == 3) {   // complex64
+            const uint3 x = *reinterpret_cast<const uint3*>(q);
             v.re = __uint_as_float(x.x);
             v.im = __uint_as_float(x.y);
+            lc = (int)x.z;
+        } else {                  // complex128
+            __builtin_memcpy(&v, q, sizeof(T));
+            lc = (int)q[W - 1];
         }
-        lc = (int)x.z;
-    } else {                          // complex128
-        __builtin_memcpy(&v, q, sizeof(T));
-        lc = (int)q[W - 1];
     }
 }
 
@@ -187,13 +148,7 @@ template <typename T>
 __device__ __forceinline__ void load_rec_at(const char* __restrict__ rb, uint32_t off, int& lc, T& v) {
     if constexpr (rec_bytes<T>() == 10) {
         const uint32_t sh = (off & 2u) * 8u;   // records start at 0 or 2 modulo 4
-        uint3 x;
-        if constexpr (SPG_REC_NT) {
-            const spg_u32x3 y = __builtin_nontemporal_load(reinterpret_cast<const spg_u32x3*>(rb + (off & ~3u)));
-            x = make_uint3(y.x, y.y, y.z);
-        } else {
-            x = *reinterpret_cast<const uint3*>(rb + (off & ~3u));
-        }
+        const uint3 x = *reinterpret_cast<const uint3*>(rb + (off & ~3u));
         const uint32_t lo = __builtin_amdgcn_alignbit(x.y, x.x, sh);
         const uint32_t hi = __builtin_amdgcn_alignbit(x.z, x.y, sh);
         v = __hiloint2double((int)hi, (int)lo);
@@ -271,11 +226,7 @@ __device__ __forceinline__ void store_rec_val(uint32_t* __restrict__ rec, int64_
 constexpr int SENT_N = 512;        // records per region: a step never runs more than 512 slots past its batch
 constexpr int SENT_REGIONS = 4;
 constexpr int DN_DUMMY = 32;       // accumulator slots past a dense tile: the sentinel records add into them
-// SPG_DN_WIDE_TWS: log2 of the widest fp64 dense tile (11: 2048 columns; 12: 4096, A/B builds)
-#ifndef SPG_DN_WIDE_TWS
-#define SPG_DN_WIDE_TWS 11
-#endif
-constexpr int DN_TW_MAX = 1 << SPG_DN_WIDE_TWS;   // widest dense tile (fp64: its accumulator's slots)
+constexpr int DN_TW_MAX = 2048;    // widest dense tile (fp64: its accumulator's slots)
 __device__ __forceinline__ int sentinel_col(int i) {
     const int r = i / SENT_N, x = i % SENT_N;
     return r == 0 ? 1024 + (x & (DN_DUMMY - 1)) : r == 1 ? 2048 + (x & (DN_DUMMY - 1))
@@ -391,13 +342,6 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t nb) {
 }
 constexpr int SYM_NWMAX = 2048;   // symbolic bitmap words: 65536 columns
 
-template <typename IP> struct SymLds {
-    uint32_t bits[SYM_NWMAX];
-    IP jb0[WAVE];
-    uint32_t joff[WAVE];
-    uint8_t mk[TILE_MK];
-};
-
 // Lane -> A-entry map for a group of up to 16 chunks (1024 products) starting at gbase.
 // Marker byte l + 1 where A entry l's products start, 0 elsewhere, stored transposed: the
 // marker of product t (group-relative) at byte 16 * (t % 64) + t / 64, so each lane reads
@@ -426,38 +370,6 @@ __device__ __forceinline__ uint64_t marker_bytes(uint4 m, int cb) {
     return (lo >> (8 * cb)) | (hi << (64 - 8 * cb));
 }
 
-// Chunks of one group (<= 16 x 64 products) U at a time: map lanes to A entries for U
-// chunks, issue all their column loads, then hand each chunk to `fn(col)` in order (lanes
-// past the group's products get col = -1).
-template <int U, typename IP, typename CT, typename L, typename F>
-__device__ __forceinline__ void walk_group(L& S, int l, int gb, int Pb, unsigned& carry,
-                                           const CT* __restrict__ Bj, F&& fn) {
-    const int nchg = min(TILE_MK, Pb - gb);
-    const uint4 mrow = reinterpret_cast<const uint4*>(S.mk)[l];
-    for (int c0 = 0; c0 < nchg; c0 += U * WAVE) {
-        const uint64_t mb = marker_bytes(mrow, c0 >> 6);
-        IP idx[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            idx[u] = (IP)-1;
-            const int cc = c0 + u * WAVE;
-            if (cc < nchg) {
-                const unsigned sp = max(wave_incl_umax_dpp((unsigned)(mb >> (8 * u)) & 0xffu), carry);
-                carry = (unsigned)readlane_i((int)sp, WAVE - 1);
-                const int src = (int)sp - 1;
-                const int t = gb + cc + l;
-                if (t < Pb) idx[u] = S.jb0[src] + (IP)(t - (int)S.joff[src]);
-            }
-        }
-        int col[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) col[u] = idx[u] >= 0 ? (int)Bj[idx[u]] : -1;
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (c0 + u * WAVE < nchg) fn(col[u]);
-    }
-}
-
 // B's column indices modulo 65536, 2 bytes each: the symbolic passes read these instead of the
 // 4-byte indices (half the bytes of the column gathers).  A symbolic tile is at most 65536
 // columns wide and aligned to its width, so it never crosses a 65536-aligned block and a
@@ -467,234 +379,26 @@ __global__ __launch_bounds__(256) void k_bj16(int64_t nnz, const int32_t* __rest
         out[i] = (uint16_t)(Bj[i] & 0xffff);
 }
 
-// Symbolic pass of the tile path over wide symbolic tiles: R = 2^(twss - tws) numeric
-// tiles at once (up to 65536 columns, the whole row for N <= 65536), so B rows are read in
-// long coalesced segments.  Writes each numeric tile's bitmap (contiguous per row) and its
-// entry count.  Columns come from Bj16 (k_bj16).
-template <typename IP>
-__global__ __launch_bounds__(TILE_WPB * WAVE) void k_tile_sym(
-    int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
-    const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
-    const uint32_t* __restrict__ sidx, uint32_t* __restrict__ bitmap, int64_t* __restrict__ item_cnt) {
-    __shared__ __attribute__((aligned(16))) SymLds<IP> lds[TILE_WPB];
-    const int l = lane_id();
-    const int wv = uniform((int)(threadIdx.x >> 6));
-    SymLds<IP>& S = lds[wv];
-    const int nw = (1 << tws) >> 5;           // words of a numeric tile
-    const int R = 1 << (twss - tws);          // numeric tiles per symbolic tile
-    const int Gs = (G + R - 1) / R;           // symbolic tiles per row
-    const uint32_t tasks = (uint32_t)(nrows * Gs);
-    const uint32_t stride = gridDim.x * TILE_WPB;
-    for (uint32_t task = xcd_block(gridDim.x) * TILE_WPB + wv; task < tasks; task += stride) {
-        const int64_t row = row0 + (int64_t)(task / (uint32_t)Gs);
-        const int gs = (int)(task % (uint32_t)Gs);
-        const int t0 = gs * R, t1 = min(G, t0 + R);
-        const int lo16 = (t0 << tws) & 0xffff;   // the tile's start inside its 65536-column block
-        const int nws = (t1 - t0) * nw;
-        const int64_t a0 = Ap[row];
-        const int nA = (int)(Ap[row + 1] - a0);
-        if (nA <= 0) {
-            for (int t = t0 + l; t < t1; t += WAVE) item_cnt[(row - row0) * G + t] = 0;
-            continue;
-        }
-        wsync();
-        for (int w = l; w < nws; w += WAVE) S.bits[w] = 0u;
-        for (int b = 0; b < nA; b += WAVE) {
-            int cnt = 0;
-            IP beg = 0;
-            if (b + l < nA) {
-                const int32_t k = Aj[a0 + b + l];
-                const IP rb = Bp[k];
-                if (Gs == 1) {
-                    cnt = (int)(Bp[k + 1] - rb);
-                    beg = rb;
-                } else {
-                    const uint32_t* sk = sidx + (int64_t)k * (Gs + 1);
-                    const uint32_t s0 = sk[gs];
-                    cnt = (int)(sk[gs + 1] - s0);
-                    beg = rb + (IP)s0;
-                }
-            }
-            const int incl = wave_incl_sum_dpp(cnt);
-            const int off = incl - cnt;
-            const int Pb = readlane_i(incl, WAVE - 1);
-            wsync();
-            S.jb0[l] = beg;
-            S.joff[l] = (uint32_t)off;
-            wsync();
-            unsigned carry = 0u;
-            for (int gb = 0; gb < Pb; gb += TILE_MK) {
-                group_markers(S, l, cnt, off, gb);
-                walk_group<8, IP>(S, l, gb, Pb, carry, Bj16, [&](int c) {
-                    if (c >= 0) set_bit(S.bits, c - lo16);
-                });
-            }
-        }
-        wsync();
-        if (bitmap) {   // (dense numeric tiles take their structure from the accumulation)
-            uint32_t* __restrict__ out = bitmap + ((row - row0) * G + t0) * (int64_t)nw;
-            for (int w = l; w < nws; w += WAVE) out[w] = S.bits[w];
-        }
-        // entry count of each numeric tile: lane t sums tile t's words (rotated start: no
-        // two lanes read one bank together)
-        for (int t = l; t < t1 - t0; t += WAVE) {
-            int c = 0;
-            for (int j = 0; j < nw; ++j) c += __popc(S.bits[t * nw + ((j + t) & (nw - 1))]);
-            item_cnt[(row - row0) * G + t0 + t] = c;
-        }
-    }
-}
-
 // Symbolic pass of the tile path, walking 16-byte WORDS of B's 16-bit columns (k_bj16) instead
 // of products (round 4).  The bitmap OR is order-free, so a wave needs no (jj, kk) product order:
 // each A entry's segment [beg, beg + cnt) of its B row inside the symbolic tile covers
 // ceil(((beg & 7) + cnt) / 8) aligned words; the words of a batch of 64 entries are flattened
 // (DPP scan of the word counts, transposed markers + max-scan for the lane -> entry map, as
-// k_tile_sym does for products) and every lane loads ONE word -- 8 columns -- per chunk of 64
-// words, masks the columns outside its entry's segment and sets their bits.  A chunk thus moves
-// up to 512 columns with one 16-byte load per lane where k_tile_sym moves 64 with one 2-byte load
-// per lane (config 5's 65-column segments: ~9 words each, 89 % of the slots used).
+// the numeric kernels do for products) and every lane loads ONE word -- 8 columns -- per chunk of
+// 64 words, masks the columns outside its entry's segment and sets their bits.  A chunk thus
+// moves up to 512 columns with one 16-byte load per lane where the product-flattened walk it
+// replaced moved 64 with one 2-byte load per lane (config 5's 65-column segments: ~9 words each,
+// 89 % of the slots used; config 5 symbolic 20.1 -> 12.1 ms).
 struct __attribute__((aligned(16))) Sym8Ent {
     uint32_t w0;     // first word (index into the uint4 view of Bj16)
     uint32_t woff;   // flattened offset of the entry's first word
     uint32_t wlen;   // words
     uint32_t lohi;   // (beg & 7) | (((beg + cnt - 1) & 7) + 1) << 8: valid halves of the first / last word
 };
-#ifndef SPG_SYM_MAXLOG
-#define SPG_SYM_MAXLOG 16   // (A/B: a narrower cap on the k_tile_sym8 tile, spgemm.hip sym_tile_log2)
-#endif
-constexpr int SYM8_NW = 1 << (SPG_SYM_MAXLOG - 5);   // k_tile_sym8 bitmap words (the widest tile)
-struct Sym8Lds {
-    uint32_t bits[SYM8_NW];
-    Sym8Ent ent[WAVE];
-    uint8_t mk[TILE_MK];
-};
-#ifndef SPG_SYM8_WPE
-#define SPG_SYM8_WPE 1   // (A/B: a waves-per-SIMD floor for k_tile_sym8's register budget)
-#endif
-template <typename IP>
-__global__ __launch_bounds__(TILE_WPB * WAVE) __attribute__((amdgpu_waves_per_eu(SPG_SYM8_WPE))) void k_tile_sym8(
-    int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
-    const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
-    const uint32_t* __restrict__ sidx, uint32_t* __restrict__ bitmap, int64_t* __restrict__ item_cnt) {
-    constexpr int U = 8;   // chunks of 64 words in flight
-    __shared__ __attribute__((aligned(16))) Sym8Lds lds[TILE_WPB];
-    const int l = lane_id();
-    const int wv = uniform((int)(threadIdx.x >> 6));
-    Sym8Lds& S = lds[wv];
-    const uint4* __restrict__ W = reinterpret_cast<const uint4*>(Bj16);
-    const int nw = (1 << tws) >> 5;           // bitmap words of a numeric tile
-    const int R = 1 << (twss - tws);          // numeric tiles per symbolic tile
-    const int Gs = (G + R - 1) / R;           // symbolic tiles per row
-    const uint32_t tasks = (uint32_t)(nrows * Gs);
-    const uint32_t stride = gridDim.x * TILE_WPB;
-    for (uint32_t task = xcd_block(gridDim.x) * TILE_WPB + wv; task < tasks; task += stride) {
-        const int64_t row = row0 + (int64_t)(task / (uint32_t)Gs);
-        const int gs = (int)(task % (uint32_t)Gs);
-        const int t0 = gs * R, t1 = min(G, t0 + R);
-        const int lo16 = (t0 << tws) & 0xffff;
-        const int nws = (t1 - t0) * nw;
-        const int64_t a0 = Ap[row];
-        const int nA = (int)(Ap[row + 1] - a0);
-        if (nA <= 0) {
-            for (int t = t0 + l; t < t1; t += WAVE) item_cnt[(row - row0) * G + t] = 0;
-            continue;
-        }
-        wsync();
-        for (int w = l; w < nws; w += WAVE) S.bits[w] = 0u;
-        for (int b = 0; b < nA; b += WAVE) {
-            int wlen = 0;
-            Sym8Ent e{0u, 0u, 0u, 0u};
-            int64_t bg = 0;
-            int cnt = 0;
-            if (b + l < nA) {
-                const int32_t k = Aj[a0 + b + l];
-                const IP rb = Bp[k];
-                if (Gs == 1) {
-                    cnt = (int)(Bp[k + 1] - rb);
-                    bg = (int64_t)rb;
-                } else {
-                    const uint32_t* sk = sidx + (int64_t)k * (Gs + 1);
-                    const uint32_t s0 = sk[gs];
-                    cnt = (int)(sk[gs + 1] - s0);
-                    bg = (int64_t)rb + s0;
-                }
-            }
-            if (cnt > 0) {
-                wlen = (int)(((bg + cnt + 7) >> 3) - (bg >> 3));
-                e.w0 = (uint32_t)(bg >> 3);
-                e.lohi = (uint32_t)(bg & 7) | ((uint32_t)(((bg + cnt - 1) & 7) + 1) << 8);
-            }
-            const int incl = wave_incl_sum_dpp(wlen);
-            const int woff = incl - wlen;
-            const int Wb = readlane_i(incl, WAVE - 1);
-            wsync();
-            e.woff = (uint32_t)woff;
-            e.wlen = (uint32_t)wlen;
-            S.ent[l] = e;
-            wsync();
-            unsigned carry = 0u;
-            for (int gb = 0; gb < Wb; gb += TILE_MK) {
-                group_markers(S, l, wlen, woff, gb);
-                const int nchg = min(TILE_MK, Wb - gb);
-                const uint4 mrow = reinterpret_cast<const uint4*>(S.mk)[l];
-                for (int c0 = 0; c0 < nchg; c0 += U * WAVE) {
-                    const uint64_t mb = marker_bytes(mrow, c0 >> 6);
-                    uint4 w[U];
-                    uint32_t lo[U], hi[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        lo[u] = 8u;   // (no valid column: slots past the group's words)
-                        hi[u] = 0u;
-                        w[u] = make_uint4(0u, 0u, 0u, 0u);
-                        const int cc = c0 + u * WAVE;
-                        if (cc < nchg) {
-                            const unsigned sp = max(wave_incl_umax_dpp((unsigned)(mb >> (8 * u)) & 0xffu), carry);
-                            carry = (unsigned)readlane_i((int)sp, WAVE - 1);
-                            const int t = gb + cc + l;
-                            if (t < Wb) {
-                                const Sym8Ent x = S.ent[(int)sp - 1];
-                                const uint32_t wi = (uint32_t)t - x.woff;
-                                lo[u] = wi == 0u ? (x.lohi & 0xffu) : 0u;
-                                hi[u] = wi + 1u == x.wlen ? (x.lohi >> 8) : 8u;
-                                w[u] = W[x.w0 + wi];
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const uint32_t ww[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
-#pragma unroll
-                        for (int h = 0; h < 8; ++h)
-                            if ((uint32_t)h >= lo[u] && (uint32_t)h < hi[u])
-                                set_bit(S.bits, (int)((ww[h >> 1] >> (16 * (h & 1))) & 0xffffu) - lo16);
-                    }
-                }
-            }
-        }
-        wsync();
-        if (bitmap) {   // (dense numeric tiles take their structure from the accumulation)
-            uint32_t* __restrict__ out = bitmap + ((row - row0) * G + t0) * (int64_t)nw;
-            for (int w = l; w < nws; w += WAVE) out[w] = S.bits[w];
-        }
-        for (int t = l; t < t1 - t0; t += WAVE) {
-            int c = 0;
-            for (int j = 0; j < nw; ++j) c += __popc(S.bits[t * nw + ((j + t) & (nw - 1))]);
-            item_cnt[(row - row0) * G + t0 + t] = c;
-        }
-    }
-}
-
-// SPG_SYM8_PF (round 6): k_tile_sym8c loads the next batch's extents during the current batch
-// (config 5 symbolic 12.0 -> 11.5 ms; 0: round 5's per-batch dependent chain)
-#ifndef SPG_SYM8_PF
-#define SPG_SYM8_PF 1
-#endif
-#ifndef SPG_SYM8_U
-#define SPG_SYM8_U 8   // (A/B: chunks of 64 words in flight in k_tile_sym8c)
-#endif
-// k_tile_sym8 with CW waves per task (round 5): the task's bitmap is shared in LDS by the
-// block's waves (the bitmap OR is order-free: ds_or from any wave), each wave walks every CW-th
+constexpr int SYM_MAXLOG = 16;                   // log2 of the widest symbolic tile (spgemm.hip sym_tile_log2)
+constexpr int SYM8_NW = 1 << (SYM_MAXLOG - 5);   // k_tile_sym8c bitmap words (the widest tile)
+// CW waves per task (round 5; before, one wave per task with a bitmap of its own): the task's
+// bitmap is shared in LDS by the block's waves (the bitmap OR is order-free: ds_or from any wave), each wave walks every CW-th
 // batch of 64 A entries with its own entry table and markers.  The 8 KB bitmap is then paid once
 // per CW waves: 12 KB per 2-wave block instead of 20 KB, so a CU holds 24 waves instead of 16
 // (config 5's symbolic pass was waiting on memory with 4 waves per SIMD).
@@ -706,12 +410,14 @@ template <int CW> struct Sym8Blk {
     uint32_t bits[SYM8_NW];
     Sym8Wave w[CW];
 };
+constexpr int SYM8_CW = 2;   // waves per task
+constexpr int SYM8_U = 8;    // chunks of 64 words in flight
 template <typename IP, int CW>
 __global__ __launch_bounds__(CW * WAVE) void k_tile_sym8c(
     int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
     const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
     const uint32_t* __restrict__ sidx, uint32_t* __restrict__ bitmap, int64_t* __restrict__ item_cnt) {
-    constexpr int U = SPG_SYM8_U;   // chunks of 64 words in flight
+    constexpr int U = SYM8_U;
     constexpr int NT = CW * WAVE;
     __shared__ __attribute__((aligned(16))) Sym8Blk<CW> blk;
     const int l = lane_id();
@@ -739,10 +445,11 @@ __global__ __launch_bounds__(CW * WAVE) void k_tile_sym8c(
         }
         for (int w = tid; w < nws; w += NT) bits[w] = 0u;
         __syncthreads();
-        // SPG_SYM8_PF (round 6): the next batch's extents (A column -> B row start and, for a
+        // (round 6) the next batch's extents (A column -> B row start and, for a
         // row cut into symbolic tiles, the tile's bounds) are loaded during this batch, as raw
         // words (unconditional loads at a clamped entry; nothing waits for them until the next
-        // batch starts) -- one dependent chain of three loads per batch no longer stalls it
+        // batch starts) -- one dependent chain of three loads per batch no longer stalls it:
+        // config 5 symbolic 12.0 -> 11.5 ms
         // (specialised for whole-row symbolic tiles, Gs == 1: no uniform branch between a load
         // and its use)
         auto batches = [&](auto gs1) {
@@ -759,36 +466,22 @@ __global__ __launch_bounds__(CW * WAVE) void k_tile_sym8c(
                     xs1 = sk[gs + 1];
                 }
             };
-            if (SPG_SYM8_PF) fetch(wv * WAVE);
+            fetch(wv * WAVE);
             for (int b = wv * WAVE; b < nA; b += NT) {
                 int wlen = 0;
                 Sym8Ent e{0u, 0u, 0u, 0u};
                 int64_t bg = 0;
                 int cnt = 0;
-                if (SPG_SYM8_PF) {
-                    if (b + l < nA) {
-                        if constexpr (decltype(gs1)::value) {
-                            cnt = (int)(xe - xr);
-                            bg = (int64_t)xr;
-                        } else {
-                            cnt = (int)(xs1 - xs0);
-                            bg = (int64_t)xr + xs0;
-                        }
-                    }
-                    fetch(b + NT);   // (unconditional: a conditional load would make the compiler wait for it)
-                } else if (b + l < nA) {
-                    const int32_t k = Aj[a0 + b + l];
-                    const IP rb = Bp[k];
-                    if (Gs == 1) {
-                        cnt = (int)(Bp[k + 1] - rb);
-                        bg = (int64_t)rb;
+                if (b + l < nA) {
+                    if constexpr (decltype(gs1)::value) {
+                        cnt = (int)(xe - xr);
+                        bg = (int64_t)xr;
                     } else {
-                        const uint32_t* sk = sidx + (int64_t)k * (Gs + 1);
-                        const uint32_t s0 = sk[gs];
-                        cnt = (int)(sk[gs + 1] - s0);
-                        bg = (int64_t)rb + s0;
+                        cnt = (int)(xs1 - xs0);
+                        bg = (int64_t)xr + xs0;
                     }
                 }
+                fetch(b + NT);   // (unconditional: a conditional load would make the compiler wait for it)
                 if (cnt > 0) {
                     wlen = (int)(((bg + cnt + 7) >> 3) - (bg >> 3));
                     e.w0 = (uint32_t)(bg >> 3);
@@ -809,7 +502,6 @@ __global__ __launch_bounds__(CW * WAVE) void k_tile_sym8c(
                     const uint4 mrow = reinterpret_cast<const uint4*>(S.mk)[l];
                     for (int c0 = 0; c0 < nchg; c0 += U * WAVE) {
                         const uint64_t mb = marker_bytes(mrow, c0 >> 6);
-                        const uint64_t mb2 = U > 8 ? marker_bytes(mrow, (c0 >> 6) + 8) : 0ull;   // (chunks 8..15 of a 16-chunk step)
                         uint4 w[U];
                         uint32_t lo[U], hi[U];
 #pragma unroll
@@ -819,7 +511,7 @@ __global__ __launch_bounds__(CW * WAVE) void k_tile_sym8c(
                             w[u] = make_uint4(0u, 0u, 0u, 0u);
                             const int cc = c0 + u * WAVE;
                             if (cc < nchg) {
-                                const unsigned sp = max(wave_incl_umax_dpp((unsigned)((u < 8 ? mb : mb2) >> (8 * (u & 7))) & 0xffu), carry);
+                                const unsigned sp = max(wave_incl_umax_dpp((unsigned)(mb >> (8 * u)) & 0xffu), carry);
                                 carry = (unsigned)readlane_i((int)sp, WAVE - 1);
                                 const int t = gb + cc + l;
                                 if (t < Wb) {
@@ -872,26 +564,18 @@ __global__ __launch_bounds__(CW * WAVE) void k_tile_sym8c(
 // (c - lo); otherwise by the popcount prefix of the symbolic bitmap, in column windows of
 // <= CAP entries (products re-read per window).
 // Ordered adds: products are taken U chunks (U * 64) at a time, all their record loads in
-// flight; then groups of RU chunks resolve collisions in owner rounds: a ds_min of the key
-// (round, chunk, lane) per product, the product whose key stuck adds, the others retry with
-// the next (smaller) round number.  Within a group the lowest (chunk, lane) -- the earliest
-// product in flattened order -- of every position adds first; groups run in order.
-// Timing-only diagnostics of k_tile (results WRONG; A/B timing builds only, never shipped):
-// 1 = no accumulation, 2 = no record loads, 4 = no product batches, 8 = no output stores.
-#ifndef SPG_TILE_DIAG
-#define SPG_TILE_DIAG 0
-#endif
-
-template <typename T, typename IP, bool DENSE, int RU>
+// flight; then chunk by chunk the products resolve collisions in owner rounds: a ds_min of the
+// key (round, chunk, lane) per product, the product whose key stuck adds, the others retry with
+// the next (smaller) round number.  Within a chunk the lowest lane -- the earliest product in
+// flattened order -- of every position adds first; chunks run in order.
+template <typename T, typename IP, bool DENSE>
 __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
     int64_t row0, int64_t nrows, int tws, int G, const IP* __restrict__ Ap,
     const int32_t* __restrict__ Aj, const T* __restrict__ Ax, int64_t K,
     const uint32_t* __restrict__ brec, const int32_t* __restrict__ tptr,
     const uint32_t* __restrict__ bitmap, const int64_t* __restrict__ item_off,
     int32_t* __restrict__ Cj, T* __restrict__ Cx, T alpha, uint32_t it_lo, uint32_t it_hi, int rgs) {
-    constexpr int diag = SPG_TILE_DIAG;   // 0 in every shipped build (timing-only diagnostics)
     constexpr int U = sizeof(T) > 8 ? 4 : 8;   // chunks in flight (complex128: half)
-    static_assert(U % RU == 0, "round groups split the chunks in flight");
     constexpr int WPB = tile_num_wpb<DENSE>();
     __shared__ __attribute__((aligned(16))) NumLds<T, IP, DENSE> lds[WPB];
     const int l = lane_id();
@@ -1006,7 +690,7 @@ __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
             if constexpr (DENSE) {   // 16-byte stores (TW is a multiple of 64)
                 uint4* a4 = reinterpret_cast<uint4*>(S.acc);
                 uint4* t4 = reinterpret_cast<uint4*>(S.tag);
-                for (int q = l; q < TW * (int)sizeof(T) / 16; q += WAVE) a4[q] = make_uint4(0u, 0u, 0u, 0u);
+                for (int q = l; q < TW / (16 / (int)sizeof(T)); q += WAVE) a4[q] = make_uint4(0u, 0u, 0u, 0u);
                 for (int q = l; q < TW / 4; q += WAVE) t4[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
             } else {
                 for (int p = l; p < span; p += WAVE) {
@@ -1019,7 +703,7 @@ __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
             // a tag below 0xfffffffe marks a column some product reached (DENSE: the
             // item's structure)
             uint32_t seq = 0x7ffffeu;
-            for (int b = 0; b < ((diag & 4) ? 0 : nA); b += WAVE) {   // (diag 4, timing only: no batches)
+            for (int b = 0; b < nA; b += WAVE) {
                 int cnt, off, Pb;
                 T bav;   // this lane's A value of the batch
                 batch(b, cnt, off, Pb, bav);
@@ -1036,7 +720,6 @@ __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
                         const int nu = min(U, (nchg - c0 + WAVE - 1) >> 6);
                         auto step = [&](auto nuc) {
                             constexpr int NU = decltype(nuc)::value;
-                            constexpr int RG = RU < NU ? RU : NU;
                             // NU chunks at once (nu of them hold products: a wave-uniform count):
                             // the lane -> A entry scans, then every record load in flight.
                             const uint64_t mb = mrow >> (8 * (c0 >> 6));
@@ -1064,13 +747,8 @@ __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
                             }
                             int qc[NU];
                             T qv[NU];
-                            if (diag & 2) {   // timing only: no record loads
 #pragma unroll
-                                for (int u = 0; u < NU; ++u) { qc[u] = (int)((idx[u] * 37u) & (uint32_t)(TW - 1)); qv[u] = (T)1; }
-                            } else {
-#pragma unroll
-                                for (int u = 0; u < NU; ++u) load_rec(brec, idx[u], qc[u], qv[u]);
-                            }
+                            for (int u = 0; u < NU; ++u) load_rec(brec, idx[u], qc[u], qv[u]);
                             int pos[NU];
                             T pv[NU];
                             uint32_t pend = 0u;
@@ -1093,23 +771,17 @@ __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
                                     pv[u] = mul_rn(av[u], qv[u]);
                                 }
                             }
-                            if (diag & 1) pend = 0u;   // timing only: no accumulation
 #pragma unroll
-                            for (int u0 = 0; u0 < NU; u0 += RG) {
-                                uint32_t gm = pend & (((1u << RG) - 1u) << u0);
+                            for (int u = 0; u < NU; ++u) {
+                                uint32_t gm = pend & (1u << u);   // this chunk's product, until it has added
                                 while (__ballot(gm != 0u)) {
-                                    const uint32_t kb = (seq << 9) | (uint32_t)l;
-#pragma unroll
-                                    for (int u = u0; u < u0 + RG && u < NU; ++u)
-                                        if (gm & (1u << u)) atomicMin(&S.tag[pos[u]], kb | ((uint32_t)u << 6));
-#pragma unroll
-                                    for (int u = u0; u < u0 + RG && u < NU; ++u)
-                                        if ((gm & (1u << u)) &&
-                                            __hip_atomic_load(&S.tag[pos[u]], __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_WAVEFRONT) == (kb | ((uint32_t)u << 6))) {
-                                            S.acc[pos[u]] = add_rn(S.acc[pos[u]], pv[u]);
-                                            gm &= ~(1u << u);
-                                        }
+                                    const uint32_t key = (seq << 9) | (uint32_t)l | ((uint32_t)u << 6);
+                                    if (gm & (1u << u)) atomicMin(&S.tag[pos[u]], key);
+                                    if ((gm & (1u << u)) && __hip_atomic_load(&S.tag[pos[u]], __ATOMIC_RELAXED,
+                                                                             __HIP_MEMORY_SCOPE_WAVEFRONT) == key) {
+                                        S.acc[pos[u]] = add_rn(S.acc[pos[u]], pv[u]);
+                                        gm &= ~(1u << u);
+                                    }
                                     --seq;
                                 }
                             }
@@ -1139,7 +811,7 @@ __global__ __launch_bounds__(tile_num_wpb<DENSE>() * WAVE) void k_tile(
                     const int c = k * WAVE + l;
                     const bool hit = S.tag[c] != 0xffffffffu;
                     const unsigned long long m = __ballot(hit);
-                    if (hit && !(diag & 8)) {   // (diag 8, timing only: no output)
+                    if (hit) {
                         const int p = run + lane_rank(m);
                         crow[p] = lo + c;
                         const T val = S.acc[c];

@@ -64,51 +64,27 @@ __global__ __launch_bounds__(WAVE) void k_lds_order_check(const T* __restrict__ 
     }
 }
 
-// C's stores and the streamed per-item reads (A rows, item offsets) with or without the
-// non-temporal hint (SPG_NT_C / SPG_NT_A, A/B builds), so they do not push the tile's B
-// slice out of the XCD's L2.
-#ifndef SPG_NT_C
-#define SPG_NT_C 1
-#endif
-// SPG_NT_A: non-temporal A-row reads in the dense-tile kernel (1, default: config 4 19.8 -> 19.4 ms;
-// the sparse-tile kernel keeps plain loads, config 5 98.7 -> 100.5 ms with them; 2: both)
-#ifndef SPG_NT_A
-#define SPG_NT_A 1
-#endif
-// SPG_NT_C: 1 non-temporal (`nt`), 0 plain, 2 agent-scope (`sc1`), 3 system-scope (`sc0 sc1`)
-// stores; A/B builds only: 4 `sc1 nt`, 5 `sc0 nt`, 6 `sc0` (vector stores in inline asm)
-#define SPG_ST_ASM(POL)                                                                               \
-    if constexpr (sizeof(T) == 8) asm volatile("global_store_dwordx2 %0, %1, off " POL ::"v"(p), "v"(v) : "memory"); \
-    else asm volatile("global_store_dword %0, %1, off " POL ::"v"(p), "v"(v) : "memory");
+// C's stores and the dense-tile kernel's streamed per-item reads (A rows, item offsets) carry the
+// non-temporal hint, so they do not push the tile's B slice out of the XCD's L2 (A reads: config 4
+// 19.8 -> 19.4 ms).  The sparse-tile kernel keeps plain A loads (ld_a<false>): config 5
+// 98.7 -> 100.5 ms with non-temporal ones.
 template <typename T> __device__ __forceinline__ void st_c(T* p, T v) {
-    if constexpr (SPG_NT_C >= 4 && (sizeof(T) == 4 || sizeof(T) == 8)) {
-        if constexpr (SPG_NT_C == 4) { SPG_ST_ASM("sc1 nt") }
-        else if constexpr (SPG_NT_C == 5) { SPG_ST_ASM("sc0 nt") }
-        else { SPG_ST_ASM("sc0") }
-    } else if constexpr (SPG_NT_C == 2 && (sizeof(T) == 4 || sizeof(T) == 8))
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else if constexpr (SPG_NT_C == 3 && (sizeof(T) == 4 || sizeof(T) == 8))
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    else if constexpr (SPG_NT_C != 0 && (sizeof(T) == 4 || sizeof(T) == 8)) __builtin_nontemporal_store(v, p);
+    if constexpr (sizeof(T) == 4 || sizeof(T) == 8) __builtin_nontemporal_store(v, p);
     else *p = v;
 }
 template <typename R> __device__ __forceinline__ void st_c(cplx<R>* p, cplx<R> v) {
     st_c(&p->re, v.re);
     st_c(&p->im, v.im);
 }
-template <bool NT = (SPG_NT_A != 0), typename T> __device__ __forceinline__ T ld_a(const T* p) {
+template <bool NT = true, typename T> __device__ __forceinline__ T ld_a(const T* p) {
     if constexpr (NT && (sizeof(T) == 4 || sizeof(T) == 8)) return __builtin_nontemporal_load(p);
     else return *p;
 }
-template <bool NT = (SPG_NT_A != 0), typename R> __device__ __forceinline__ cplx<R> ld_a(const cplx<R>* p) {
+template <bool NT = true, typename R> __device__ __forceinline__ cplx<R> ld_a(const cplx<R>* p) {
     return cplx<R>(ld_a<NT>(&p->re), ld_a<NT>(&p->im));
 }
-constexpr bool SP_NT_A = SPG_NT_A == 2;   // (the sparse-tile kernels)
 
 constexpr int DN_WPB = 2;     // waves per block
-#ifndef SPG_RG_SYNC
-#define SPG_RG_SYNC 1   // items between the barriers of a cooperative record-group block
-#endif
 
 // Per-batch A-entry table: the byte offset of the entry's first product record, shifted by
 // the entry's flattened offset (so product t of the batch reads base[src] + t * RB), and the
@@ -123,18 +99,15 @@ template <typename T> struct __attribute__((aligned(16))) DnEnt {
 };
 
 
-// fp64 items take their structure from the accumulator itself (SPG_DN_SENT): every slot
+// Real-valued items take their structure from the accumulator itself (dn_sent): every slot
 // starts at -0.0 instead of +0.0.  -0.0 + p == +0.0 + p for every p except p == -0.0, so a
 // column's sum equals scipy's (which starts at +0.0) except while every product it has seen
 // is -0.0 (ours -0.0, scipy's +0.0).  So a column is reached iff its slot is not -0.0 or it
 // saw only -0.0 products; the item's symbolic count tells which case holds: fewer non -0.0
 // slots than entries sends the item down a rare path that re-walks its products and turns
 // each reached -0.0 slot into scipy's +0.0.  No hit byte per product.
-#ifndef SPG_DN_SENT
-#define SPG_DN_SENT 1
-#endif
 template <typename T> constexpr bool dn_sent() {
-    return SPG_DN_SENT && (std::is_same<T, double>::value || std::is_same<T, float>::value);
+    return std::is_same<T, double>::value || std::is_same<T, float>::value;   // (complex: a hit byte per column)
 }
 // the -0.0 sentinel's bits and the bits of a real value
 template <typename T> __device__ __forceinline__ bool is_neg_zero(T v) {
@@ -146,10 +119,7 @@ template <typename T> __device__ __forceinline__ bool is_neg_zero(T v) {
 // record loads in flight together: 16 for the widest kernels (2048-slot accumulators: LDS
 // holds them to 2 waves per SIMD, so the extra registers are free; round 4, config 4
 // numeric -2 %, config 5 -1 %), 8 for the 1024-slot ones (4 waves per SIMD at <= 128 VGPRs).
-#ifndef SPG_DN_U16
-#define SPG_DN_U16 1
-#endif
-__host__ __device__ constexpr int dn_mkb(int slots) { return (SPG_DN_U16 && slots >= 2048) ? 16 : 8; }
+__host__ __device__ constexpr int dn_mkb(int slots) { return slots >= 2048 ? 16 : 8; }
 
 template <typename T, int TWD, bool HIT = !dn_sent<T>()> struct DnLds {
     T acc[TWD + DN_DUMMY];        // accumulator by column; + the sentinel records' slots
@@ -163,9 +133,6 @@ template <typename T, int TWD> struct DnLds<T, TWD, false> {
     T acc[TWD + DN_DUMMY];
     DnEnt<T> ent[WAVE + 1];
     uint8_t mk[dn_mkb(TWD) * WAVE];
-#ifdef SPG_LDS_PAD
-    uint8_t pad[SPG_LDS_PAD];   // (A/B builds: occupancy sensitivity)
-#endif
 };
 
 
@@ -262,24 +229,15 @@ __device__ __forceinline__ void dn_batch(L* lp, T* acc, int l, int cnt, uint32_t
                         eb = e.base;
                         qa[u] = e.a;
                     }
-                    if constexpr ((SPG_TILE_DIAG & 2) != 0) {   // timing only: no record loads
-                        qc[u] = (int)(((eb + t * 2654435761u) >> 22) & 1023u);
-                        qv[u] = (T)1;
-                    } else {
-                        load_rec_at(rb, eb + __umul24(t, RB), qc[u], qv[u]);
-                    }
+                    load_rec_at(rb, eb + __umul24(t, RB), qc[u], qv[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
                     const int c = slot(qc[u]);
-                    if constexpr ((SPG_TILE_DIAG & 16) != 0) {   // timing only: plain LDS stores
-                        acc[c] = mul_rn(qa[u], qv[u]);
-                    } else if constexpr ((SPG_TILE_DIAG & 32) != 0) {   // timing only: conflict-free adds
-                        lds_add(&acc[l + (c & 1)], mul_rn(qa[u], qv[u]));
-                    } else if constexpr ((SPG_TILE_DIAG & 1) == 0 && OrderedLdsAdd<T>::value) {   // (diag 1: none)
+                    if constexpr (OrderedLdsAdd<T>::value) {
                         lds_add(&acc[c], mul_rn(qa[u], qv[u]));   // chunk order = issue order
                         hit(c);
-                    } else if constexpr ((SPG_TILE_DIAG & 1) == 0) {
+                    } else {
                         // fp32 (round 5): ds_add_f32 costs 193 CU-cycles per wave instruction on
                         // MI355X, a plain read-add-write 17.  The products of ONE A entry in a
                         // chunk hit distinct columns (a B row's columns are distinct), so the
@@ -388,13 +346,8 @@ template <typename T, int TWD>
 __device__ __forceinline__ void dn_emit(DnLds<T, TWD>& S, int l, int TW, int lo, int nnz, const int32_t* __restrict__ tp,
                                         int64_t a0, int nA, const int32_t* __restrict__ Aj,
                                         const char* __restrict__ rb, int32_t* __restrict__ crow,
-                                        T* __restrict__ xrow, T alpha, int rgs, int32_t* cj0 = nullptr,
-                                        T* cx0 = nullptr) {
+                                        T* __restrict__ xrow, T alpha, int rgs) {
     constexpr uint32_t RB = (uint32_t)rec_bytes<T>();
-    // (diag 1024, timing only: every store full and aligned, into a per-wave 64-entry region of C)
-    const uint32_t wreg = ((blockIdx.x * DN_WPB + (threadIdx.x >> 6)) & 4095u) * 64u;
-    int32_t* crow_al = cj0 + wreg;
-    T* xrow_al = cx0 + wreg;
     wsync();
     // the item's structure, 64 columns at a time: hit[] or (dn_sent) the non -0.0 slots
     // (4 column groups per round: their LDS reads in flight together, TW >= 256)
@@ -413,12 +366,8 @@ __device__ __forceinline__ void dn_emit(DnLds<T, TWD>& S, int l, int TW, int lo,
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned long long m = __ballot(h[e]);
-                if constexpr ((SPG_TILE_DIAG & 1024) != 0) {   // (diag 1024: full aligned 64-lane stores)
-                    st_c(crow_al + l, (int32_t)(lo + (k0 + e) * WAVE + l));
-                    st_c(xrow_al + l, v[e]);
-                } else if (h[e] && (SPG_TILE_DIAG & 8) == 0) {   // (diag 8, timing only: no output)
-                    uint32_t p = (uint32_t)(run + lane_rank(m));
-                    if constexpr ((SPG_TILE_DIAG & 128) != 0) p &= 63u;   // (diag 128: the same stores, L2-resident)
+                if (h[e]) {
+                    const uint32_t p = (uint32_t)(run + lane_rank(m));
                     st_c(crow + p, (int32_t)(lo + (k0 + e) * WAVE + l));
                     st_c(xrow + p, decltype(one)::value ? v[e] : mul_rn(alpha, v[e]));
                 }
@@ -430,7 +379,7 @@ __device__ __forceinline__ void dn_emit(DnLds<T, TWD>& S, int l, int TW, int lo,
     const bool one = alpha == (T)1;
     const int got = one ? emit(std::true_type{}) : emit(std::false_type{});
     if constexpr (dn_sent<T>()) {
-        if (got < nnz && (SPG_TILE_DIAG & 9) == 0) {
+        if (got < nnz) {
             // rare: a reached column saw only -0.0 products -- its slot is still -0.0, scipy's
             // sum is +0.0.  Re-walk the item's records (one lane per A entry) and turn every
             // reached -0.0 slot into +0.0, then write the item again.
@@ -476,29 +425,27 @@ __device__ __forceinline__ void dn_item(DnLds<T, TWD>& S, int l, int TW, int lo,
                                         const int32_t* __restrict__ Aj,
                                         const T* __restrict__ Ax, const char* __restrict__ rb, uint32_t sent,
                                         int32_t* __restrict__ crow,
-                                        T* __restrict__ xrow, T alpha, int rgs, int32_t* cj0, T* cx0) {
+                                        T* __restrict__ xrow, T alpha, int rgs) {
     dn_clear(S, l, TW);
     dn_walk<T, NB, dn_mkb(TWD)>(&S, S.acc, l, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, rgs, [&](int c) { return c; },
                    [&](int c) {
                        if constexpr (!dn_sent<T>()) S.hit[c] = 1;
                    });
-    dn_emit<T, TWD>(S, l, TW, lo, nnz, tp, a0, nA, Aj, rb, crow, xrow, alpha, rgs, cj0, cx0);
+    dn_emit<T, TWD>(S, l, TW, lo, nnz, tp, a0, nA, Aj, rb, crow, xrow, alpha, rgs);
 }
 // Numeric pass on dense tiles: one wave per (row, tile) item, items tile-major over the
 // XCD-aware block map (an XCD works through one tile at a time, so the tile's B slice and
 // segment table stay in its L2), the first NB batches' A entries and tile segments loaded up
-// front.
-// RG = 1: the two waves of a block take independent items (tile-major).  RG = DN_WPB (A/B
-// builds, SPG_DN_RGS): the block's two waves take the two tiles of one record group of the same
-// row (items group-major), starting together every SPG_RG_SYNC items, as k_tile_sp<.., RG>.
-template <typename T, typename IP, int TWD, int RG = 1>
+// front.  The two waves of a block take independent items (tile-major); the two tiles of one
+// record group of the same row per block, as k_tile_sp<.., RG>, measured slower (spgemm.hip,
+// record_group_log2).
+template <typename T, typename IP, int TWD>
 __global__ __launch_bounds__(DN_WPB * WAVE) void k_tile_dn(
     int64_t row0, int64_t nrows, int tws, int G, const IP* __restrict__ Ap,
     const int32_t* __restrict__ Aj, const T* __restrict__ Ax, int64_t K,
     const uint32_t* __restrict__ brec, const int32_t* __restrict__ tptr,
     const int64_t* __restrict__ item_off, int32_t* __restrict__ Cj, T* __restrict__ Cx, T alpha, uint32_t sent,
     uint32_t it_lo, uint32_t it_hi, int rgs) {
-    static_assert(RG == 1 || RG == DN_WPB, "a record group is the block's waves");
     static_assert(OrderedLdsAdd<T>::value || std::is_same<T, float>::value, "ordered LDS add or fp32 runs");
     constexpr int NB = sizeof(T) > 8 ? 4 : 8;    // A batches preloaded per item
     __shared__ __attribute__((aligned(16))) DnLds<T, TWD> lds[DN_WPB];
@@ -507,19 +454,10 @@ __global__ __launch_bounds__(DN_WPB * WAVE) void k_tile_dn(
     DnLds<T, TWD>& S = lds[wv];
     const int TW = 1 << tws;
     const char* __restrict__ rb = reinterpret_cast<const char*>(brec);
-    // items [it_lo, it_hi) (tile-major: a range of whole tiles; rows*G < 2^31 on the host;
-    // RG > 1: (record group, row) items, one per block)
-    constexpr uint32_t PER = RG > 1 ? 1u : (uint32_t)DN_WPB;
-    uint32_t sweep = 0;
-    for (uint32_t it = it_lo + xcd_block(gridDim.x) * PER + (RG > 1 ? 0u : (uint32_t)wv); it < it_hi;
-         it += gridDim.x * PER, ++sweep) {
-        if constexpr (RG > 1) {
-            if (sweep % SPG_RG_SYNC == 0) __syncthreads();
-        }
-        const int grp = (int)(it / (uint32_t)nrows);
-        const int64_t row = row0 + (int64_t)(it - (uint32_t)grp * (uint32_t)nrows);
-        const int g = RG > 1 ? grp * RG + wv : grp;
-        if (RG > 1 && g >= G) continue;   // (a padding tile of the last group)
+    // items [it_lo, it_hi) (tile-major: a range of whole tiles; rows*G < 2^31 on the host)
+    for (uint32_t it = it_lo + xcd_block(gridDim.x) * DN_WPB + (uint32_t)wv; it < it_hi; it += gridDim.x * DN_WPB) {
+        const int g = (int)(it / (uint32_t)nrows);
+        const int64_t row = row0 + (int64_t)(it - (uint32_t)g * (uint32_t)nrows);
         const int64_t item = (row - row0) * G + g;
         const int64_t obase = ld_a(item_off + item);
         const int nnz = (int)(ld_a(item_off + item + 1) - obase);
@@ -542,7 +480,7 @@ __global__ __launch_bounds__(DN_WPB * WAVE) void k_tile_dn(
 #pragma unroll
         for (int q = 0; q < NB; ++q) sq[q] = kq[q] >= 0 ? seg_pair(tp, kq[q], rgs) : make_uint2(0u, 0u);
         dn_item<T, NB, TWD>(S, l, TW, g * TW, nnz, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, Cj + obase, Cx + obase, alpha,
-                            rgs, Cj, Cx);
+                            rgs);
     }
 }
 
@@ -568,22 +506,15 @@ template <int CAP_, int NW_, int DUMMY_, int MKB_> struct SpCfg {
 };
 using SpCfg1024 = SpCfg<1024, 128, WAVE, 8>;    // tiles of <= 4096 columns (11.3 KB per wave)
 using SpCfg2048 = SpCfg<2048, 256, WAVE, 16>;   // fp64 8192-column tiles (21.0 KB)
-// fp64 8192-column tiles in cooperative blocks of RG waves (k_tile_sp<.., RG>, A/B builds with
-// SPG_SP_RGS > 0): 20,432 bytes per wave, so two 4-wave blocks (8 waves) fit a CU's 160 KB;
+// fp64 8192-column tiles in cooperative blocks of RG waves (k_tile_sp<.., RG>): 20,432 bytes per wave, so two 4-wave blocks (8 waves) fit a CU's 160 KB;
 // 2032 slots per window (config 5's items hold 1887 +- 40 entries) and 8 lane slots (an
 // out-of-window add conflicts at most 8 ways)
-#ifndef SPG_RG_MKB
-#define SPG_RG_MKB 16   // (A/B: chunks per marker group of the cooperative kernel)
-#endif
-using SpCfgRG = SpCfg<2032, 256, 8, SPG_RG_MKB>;
+using SpCfgRG = SpCfg<2032, 256, 8, 16>;
 template <typename T, typename CF> struct SpLds {
     T acc[CF::CAP + CF::DUMMY];         // compact accumulator of one window; + lane slots
     uint2 bw[CF::NW];                   // (bitmap word, popcount prefix)
     DnEnt<T> ent[WAVE + 1];
     uint8_t mk[CF::MKB * WAVE];
-#ifdef SPG_LDS_PAD
-    uint8_t pad[SPG_LDS_PAD];   // (A/B builds: occupancy sensitivity)
-#endif
 };
 
 // RG = 1: one-wave blocks, items tile-major (item it = (tile, row)).
@@ -620,13 +551,9 @@ void k_tile_sp(
     const char* __restrict__ rb = reinterpret_cast<const char*>(brec);
     const bool one = alpha == (T)1;
     // one item per block and sweep (RG == 1: a one-wave block's; RG > 1: the group's RG tiles of a row)
-    uint32_t sweep = 0;
-    for (uint32_t it = it_lo + xcd_block(gridDim.x); it < it_hi; it += gridDim.x, ++sweep) {
-        // RG > 1: the block's waves start together every SPG_RG_SYNC items (a persistent grid:
-        // between two barriers a wave that finishes early starts its next item)
-        if constexpr (RG > 1) {
-            if (sweep % SPG_RG_SYNC == 0) __syncthreads();
-        }
+    for (uint32_t it = it_lo + xcd_block(gridDim.x); it < it_hi; it += gridDim.x) {
+        // RG > 1: the block's waves start every item together (a persistent grid)
+        if constexpr (RG > 1) __syncthreads();
         const int grp = (int)(it / (uint32_t)nrows);
         const int64_t row = row0 + (int64_t)(it - (uint32_t)grp * (uint32_t)nrows);
         const int g = RG == 1 ? grp : grp * RG + wv;
@@ -673,8 +600,8 @@ void k_tile_sp(
                 kq[q] = -1;
                 aq[q] = (T)0;
                 if (q * WAVE + l < nA) {
-                    kq[q] = ld_a<SP_NT_A>(Aj + a0 + q * WAVE + l);
-                    aq[q] = ld_a<SP_NT_A>(Ax + a0 + q * WAVE + l);
+                    kq[q] = ld_a<false>(Aj + a0 + q * WAVE + l);
+                    aq[q] = ld_a<false>(Ax + a0 + q * WAVE + l);
                 }
             }
 #pragma unroll
@@ -714,49 +641,47 @@ void k_tile_sp(
                            },
                            [&](int) {});
             wsync();
-            if ((SPG_TILE_DIAG & 8) == 0) {   // (diag 8, timing only: no output)
-                // values: the window's slots are its entries in C order
-                T* __restrict__ xw = Cx + obase + wb;
-                auto vals = [&](auto one) {   // 4 rows of 64 slots per round, reads first
-                    for (int p0 = 0; p0 < wn; p0 += 4 * WAVE) {
-                        T v[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = S.acc[min(p0 + e * WAVE + l, SP_CAP + SP_DUMMY - 1)];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int p = p0 + e * WAVE + l;
-                            if (p < wn) st_c(xw + p, decltype(one)::value ? v[e] : mul_rn(alpha, v[e]));
-                        }
-                    }
-                };
-                if (one) vals(std::true_type{});
-                else vals(std::false_type{});
-                wsync();
-                // columns: each window lane lists its words' set bits at their ranks
-                uint32_t* __restrict__ cl = reinterpret_cast<uint32_t*>(S.acc);
-                if (l >= L0 && l < L1) {
-                    int pos = p0 - wb;
-#pragma unroll
-                    for (int q = 0; q < SP_WPL; ++q) {
-                        uint32_t w = wd[q];
-                        const int cb = lo + 32 * (w0 + q);
-                        while (w != 0u) {
-                            cl[pos++] = (uint32_t)(cb + __builtin_ctz(w));
-                            w &= w - 1u;
-                        }
-                    }
-                }
-                wsync();
-                int32_t* __restrict__ cw = Cj + obase + wb;
+            // values: the window's slots are its entries in C order
+            T* __restrict__ xw = Cx + obase + wb;
+            auto vals = [&](auto one) {   // 4 rows of 64 slots per round, reads first
                 for (int p0 = 0; p0 < wn; p0 += 4 * WAVE) {
-                    uint32_t v[4];
+                    T v[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = cl[min(p0 + e * WAVE + l, SP_CAP - 1)];
+                    for (int e = 0; e < 4; ++e) v[e] = S.acc[min(p0 + e * WAVE + l, SP_CAP + SP_DUMMY - 1)];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int p = p0 + e * WAVE + l;
-                        if (p < wn) st_c(cw + p, (int32_t)v[e]);
+                        if (p < wn) st_c(xw + p, decltype(one)::value ? v[e] : mul_rn(alpha, v[e]));
                     }
+                }
+            };
+            if (one) vals(std::true_type{});
+            else vals(std::false_type{});
+            wsync();
+            // columns: each window lane lists its words' set bits at their ranks
+            uint32_t* __restrict__ cl = reinterpret_cast<uint32_t*>(S.acc);
+            if (l >= L0 && l < L1) {
+                int pos = p0 - wb;
+#pragma unroll
+                for (int q = 0; q < SP_WPL; ++q) {
+                    uint32_t w = wd[q];
+                    const int cb = lo + 32 * (w0 + q);
+                    while (w != 0u) {
+                        cl[pos++] = (uint32_t)(cb + __builtin_ctz(w));
+                        w &= w - 1u;
+                    }
+                }
+            }
+            wsync();
+            int32_t* __restrict__ cw = Cj + obase + wb;
+            for (int p0 = 0; p0 < wn; p0 += 4 * WAVE) {
+                uint32_t v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = cl[min(p0 + e * WAVE + l, SP_CAP - 1)];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int p = p0 + e * WAVE + l;
+                    if (p < wn) st_c(cw + p, (int32_t)v[e]);
                 }
             }
             L0 = L1;
@@ -773,40 +698,28 @@ void k_tile_sp(
 // loads -- a wave load costs the same per instruction whether it moves 4 or 16 bytes per lane,
 // abtest/gather_probe -- instead of 4-byte ones: a quarter of the load instructions.)
 // Writes each numeric tile's entry count (and, for sparse numeric tiles, its bitmap), as
-// k_tile_sym.  (Measured on config 4: 4.05 ms against 7.05 ms for k_tile_sym's flattened
+// k_tile_sym8c.  (Measured on config 4: 4.05 ms against 7.05 ms for a product-flattened
 // walk over 16384-column tiles and 7.0 ms for a one-entry-per-instruction cursor walk.)
 constexpr int SEG_WPB = 2;
-#ifndef SPG_SYM_NQ
-#define SPG_SYM_NQ 4   // (A/B: quads of A entries per round of k_tile_sym_seg)
-#endif
-// SPG_SYM_PF (round 6): the first SPG_SYM_PF steps of a k_tile_sym_seg round load together, with
-// the next round's extents loaded under them (config 4 symbolic 2.74 -> 2.51 ms; 0: round 5's loop).
-// 3 steps in flight cost 151 VGPRs = 3 waves per SIMD; 2 steps fit the 128 of 4 waves per SIMD
-// (SPG_SYM_SEG_OCC) without a spill, and 16 waves per CU beat the third step: config 4 symbolic
-// 2.52 -> 2.29 ms (3 steps capped at 128 VGPRs spill, 2.62 ms; 1 step 2.45 ms, or 2.32 ms at 5 waves
-// per SIMD; 2 steps at 5 waves spill, 2.73 ms: profiles/sym_flags.txt)
-#ifndef SPG_SYM_PF
-#define SPG_SYM_PF 2
-#endif
-#ifndef SPG_SYM_SEG_OCC
-#define SPG_SYM_SEG_OCC 4   // waves per SIMD k_tile_sym_seg's register allocation must allow (0: the compiler's choice)
-#endif
-// SPG_SYM_DIAG (timing only, A/B builds): k_tile_sym_seg<IP, true> -- every load, one of a lane's
-// eight marks per load -- runs before each k_tile_sym_seg launch, which then writes the counts.
-#ifndef SPG_SYM_DIAG
-#define SPG_SYM_DIAG 0
-#endif
+constexpr int SYM_NQ = 4;   // quads of A entries per round: 16 entries, 4 loads in flight per lane
+// (Round 6) the first SYM_PF steps of a round load together, with the next round's extents loaded
+// under them (config 4 symbolic 2.74 -> 2.51 ms).  3 steps in flight cost 151 VGPRs = 3 waves per
+// SIMD; 2 steps fit the 128 of 4 waves per SIMD (the kernel's amdgpu_waves_per_eu) without a
+// spill, and 16 waves per CU beat the third step: config 4 symbolic 2.52 -> 2.29 ms (3 steps
+// capped at 128 VGPRs spill, 2.62 ms; 1 step 2.45 ms, or 2.32 ms at 5 waves per SIMD; 2 steps at
+// 5 waves spill, 2.73 ms: profiles/sym_flags.txt)
+constexpr int SYM_PF = 2;
 // The walk of one symbolic task (row, symbolic tile gs of Gs) by one wave: rounds of 4 * NQ A
 // entries starting at entry b0, bstep entries apart (a wave alone on its task: b0 = 0, bstep =
 // 4 * NQ; W waves sharing one: wave w takes b0 = 4 * NQ * w, bstep = 4 * NQ * W).  Every column
 // of the task's B segments goes to mark(column mod 65536), in no particular order;
 // stop(b) -> true before the round at entry b ends the walk.
-template <typename IP, bool DIAG = false, typename Mark, typename Stop>
+template <typename IP, typename Mark, typename Stop>
 __device__ __forceinline__ void sym_seg_walk(int l, int64_t a0, int nA, int b0, int bstep, int gs, int Gs,
                                              const int32_t* __restrict__ Aj, const IP* __restrict__ Bp,
                                              const uint16_t* __restrict__ Bj16, const uint32_t* __restrict__ sidx,
                                              Mark&& mark, Stop&& stop) {
-    constexpr int NQ = SPG_SYM_NQ;   // quads of A entries per round: 16 entries, 4 loads in flight per lane
+    constexpr int NQ = SYM_NQ;
     const int sub = l & 15, grp = l >> 4;
     {
         // NQ quads of entries (4 per quad, one per 16-lane group) per round; the next round's
@@ -849,8 +762,7 @@ __device__ __forceinline__ void sym_seg_walk(int l, int64_t a0, int nA, int b0, 
                 const int x = e + 8 * sub;
                 const uint32_t ww[4] = {w[q].x, w[q].y, w[q].z, w[q].w};
 #pragma unroll
-                for (int h0 = 0; h0 < (DIAG ? 1 : 8); ++h0) {
-                    const int h = DIAG ? (l & 7) : h0;   // (DIAG: a lane-dependent one, so the load stays 16 bytes)
+                for (int h = 0; h < 8; ++h) {
                     const int xh = x + h;
                     if (xh >= odd[q] && xh < span[q]) mark((int)((ww[h >> 1] >> (16 * (h & 1))) & 0xffffu));
                 }
@@ -859,12 +771,12 @@ __device__ __forceinline__ void sym_seg_walk(int l, int64_t a0, int nA, int b0, 
         // (the loop is specialised for whole-row symbolic tiles, Gs == 1, so no uniform branch on
         // it sits between a load and its use)
         auto rounds = [&](auto gs1) {
-            IP xr0[NQ], xr1[NQ];       // (SPG_SYM_PF: the next round's B row starts / ends,
+            IP xr0[NQ], xr1[NQ];       // (the next round's B row starts / ends,
             uint32_t xs0[NQ], xs1[NQ];  // or its symbolic-tile bounds, as loaded)
             bool pend = false;
             for (int b = b0; b < nA; b += bstep) {
                 if (stop(b)) break;
-                if (SPG_SYM_PF > 0 && pend) {   // this round's extents from the raw words loaded last round
+                if (pend) {   // this round's extents from the raw words loaded last round
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) {
                         const bool ok = b + 4 * q + grp < nA;
@@ -888,54 +800,48 @@ __device__ __forceinline__ void sym_seg_walk(int l, int64_t a0, int nA, int b0, 
                 mx = max(mx, __shfl_xor(mx, 16, WAVE));
                 mx = max(mx, __shfl_xor(mx, 32, WAVE));
                 mx = uniform(mx);
-                int e0 = 0;
-                if constexpr (SPG_SYM_PF > 0) {
-                    // round 6: the next round's A columns first, then this round's first SPG_SYM_PF
-                    // steps of column loads (unconditional: an index past the segment re-reads its
-                    // last 16 bytes and is masked), then the next round's B extents (waiting only for
-                    // the A columns: the column loads stay in flight), then the ORs: about one memory
-                    // round trip per round instead of one per step plus a dependent chain per quad
-                    int32_t kn[NQ];
+                // round 6: the next round's A columns first, then this round's first SYM_PF
+                // steps of column loads (unconditional: an index past the segment re-reads its
+                // last 16 bytes and is masked), then the next round's B extents (waiting only for
+                // the A columns: the column loads stay in flight), then the ORs: about one memory
+                // round trip per round instead of one per step plus a dependent chain per quad
+                int32_t kn[NQ];
 #pragma unroll
-                    for (int q = 0; q < NQ; ++q) kn[q] = Aj[a0 + min(b + bstep + 4 * q + grp, nA - 1)];
-                    uint4 w[SPG_SYM_PF > 0 ? SPG_SYM_PF : 1][NQ];
+                for (int q = 0; q < NQ; ++q) kn[q] = Aj[a0 + min(b + bstep + 4 * q + grp, nA - 1)];
+                uint4 w[SYM_PF][NQ];
 #pragma unroll
-                    for (int st = 0; st < SPG_SYM_PF; ++st)
-#pragma unroll
-                        for (int q = 0; q < NQ; ++q) {
-                            const int last = max(span[q] - 1, 0) >> 3;
-                            w[st][q] = w0[q][min((st * 128 + 8 * sub) >> 3, last)];
-                        }
-                    // (raw words only: they are combined at the next round's start, so nothing waits
-                    // for them before the ORs)
+                for (int st = 0; st < SYM_PF; ++st)
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) {
-                        xr0[q] = Bp[kn[q]];
-                        if constexpr (decltype(gs1)::value) {
-                            xr1[q] = Bp[kn[q] + 1];
-                        } else {
-                            const uint32_t* sk = sidx + (int64_t)kn[q] * (Gs + 1);
-                            xs0[q] = sk[gs];
-                            xs1[q] = sk[gs + 1];
-                        }
+                        const int last = max(span[q] - 1, 0) >> 3;
+                        w[st][q] = w0[q][min((st * 128 + 8 * sub) >> 3, last)];
                     }
-                    pend = true;
+                // (raw words only: they are combined at the next round's start, so nothing waits
+                // for them before the ORs)
 #pragma unroll
-                    for (int st = 0; st < SPG_SYM_PF; ++st)
-                        if (st * 128 < mx) or_step(st * 128, w[st]);
-                    e0 = SPG_SYM_PF * 128;
+                for (int q = 0; q < NQ; ++q) {
+                    xr0[q] = Bp[kn[q]];
+                    if constexpr (decltype(gs1)::value) {
+                        xr1[q] = Bp[kn[q] + 1];
+                    } else {
+                        const uint32_t* sk = sidx + (int64_t)kn[q] * (Gs + 1);
+                        xs0[q] = sk[gs];
+                        xs1[q] = sk[gs + 1];
+                    }
                 }
-                for (int e = e0; e < mx; e += 128) {
-                    uint4 w[NQ];
+                pend = true;
+#pragma unroll
+                for (int st = 0; st < SYM_PF; ++st)
+                    if (st * 128 < mx) or_step(st * 128, w[st]);
+                for (int e = SYM_PF * 128; e < mx; e += 128) {   // (longer spans: one step at a time)
+                    uint4 we[NQ];
 #pragma unroll
                     for (int q = 0; q < NQ; ++q) {
                         const int x = e + 8 * sub;
-                        w[q] = x < span[q] ? w0[q][x >> 3] : make_uint4(0u, 0u, 0u, 0u);
+                        we[q] = x < span[q] ? w0[q][x >> 3] : make_uint4(0u, 0u, 0u, 0u);
                     }
-                    if (SPG_SYM_PF == 0 && e == 0) extents(b + bstep, cnt, beg);   // (next round; span/odd/w0 are kept)
-                    or_step(e, w);
+                    or_step(e, we);
                 }
-                if (SPG_SYM_PF == 0 && mx == 0) extents(b + bstep, cnt, beg);
             }
         };
         if (Gs == 1) rounds(std::true_type{});
@@ -948,13 +854,8 @@ __device__ __forceinline__ void sym_seg_walk(int l, int64_t a0, int nA, int b0, 
 // A entries the wave counts its bitmap, and a task whose columns [lo, min(lo + width, ncols))
 // are all set stops walking -- later products cannot add a column (config 3 at density 0.1:
 // C rows 100 % dense, ~90 of 819 A entries fill a row).
-#if SPG_SYM_SEG_OCC > 0
-#define SPG_SYM_SEG_ATTR __attribute__((amdgpu_waves_per_eu(SPG_SYM_SEG_OCC)))
-#else
-#define SPG_SYM_SEG_ATTR
-#endif
-template <typename IP, bool DIAG = false>
-__global__ __launch_bounds__(SEG_WPB * WAVE) SPG_SYM_SEG_ATTR void k_tile_sym_seg(
+template <typename IP>
+__global__ __launch_bounds__(SEG_WPB * WAVE) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_sym_seg(
     int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
     const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
     const uint32_t* __restrict__ sidx, uint32_t* __restrict__ bitmap, int64_t* __restrict__ item_cnt,
@@ -985,8 +886,8 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) SPG_SYM_SEG_ATTR void k_tile_sym_se
         wsync();
         // the task's valid columns (the last tile of a row may pass the matrix's last column)
         const int full = ncols > 0 ? (int)min((int64_t)nws * 32, ncols - ((int64_t)t0 << tws)) : 0;
-        sym_seg_walk<IP, DIAG>(
-            l, a0, nA, 0, 4 * SPG_SYM_NQ, gs, Gs, Aj, Bp, Bj16, sidx, [&](int c16) { set_bit(bits, c16 - lo16); },
+        sym_seg_walk<IP>(
+            l, a0, nA, 0, 4 * SYM_NQ, gs, Gs, Aj, Bp, Bj16, sidx, [&](int c16) { set_bit(bits, c16 - lo16); },
             [&](int b) {
                 if (full <= 0 || b == 0 || (b & (WAVE - 1)) != 0) return false;   // every 64 entries: full yet?
                 wsync();
@@ -1022,19 +923,10 @@ __global__ __launch_bounds__(SEG_WPB * WAVE) SPG_SYM_SEG_ATTR void k_tile_sym_se
 // 16-byte stores by all waves; wave w walks rounds w, w + W, ... (sym_seg_walk); then wave w
 // counts the numeric tiles t = w, w + W, ... of the task, 16 flag bytes per lane and read (the
 // flags are 0 or 1, so a word's popcount is its sum).
-#ifndef SPG_SYM_FLAG_W
-#define SPG_SYM_FLAG_W 8   // waves per block (config 4: 2 6.34, 4 3.69, 6 5.29, 8 2.63-3.32 ms, profiles/sym_flags.txt)
-#endif
-#ifndef SPG_SYM_FLAG_OCC
-#define SPG_SYM_FLAG_OCC 4   // waves per SIMD the register allocation must allow: two 8-wave blocks per CU
-#endif
-#if SPG_SYM_FLAG_OCC > 0
-#define SPG_SYM_FLAG_ATTR __attribute__((amdgpu_waves_per_eu(SPG_SYM_FLAG_OCC)))
-#else
-#define SPG_SYM_FLAG_ATTR
-#endif
+constexpr int SYM_FLAG_W = 8;   // waves per block (config 4: 2 6.34, 4 3.69, 6 5.29, 8 2.63-3.32 ms, profiles/sym_flags.txt)
+// (amdgpu_waves_per_eu(4): the register allocation must allow two 8-wave blocks per CU)
 template <typename IP, int W>
-__global__ __launch_bounds__(W * WAVE) SPG_SYM_FLAG_ATTR void k_tile_sym_flag(
+__global__ __launch_bounds__(W * WAVE) __attribute__((amdgpu_waves_per_eu(4))) void k_tile_sym_flag(
     int64_t row0, int64_t nrows, int tws, int G, int twss, const IP* __restrict__ Ap,
     const int32_t* __restrict__ Aj, const IP* __restrict__ Bp, const uint16_t* __restrict__ Bj16,
     const uint32_t* __restrict__ sidx, int64_t* __restrict__ item_cnt) {
@@ -1062,7 +954,7 @@ __global__ __launch_bounds__(W * WAVE) SPG_SYM_FLAG_ATTR void k_tile_sym_flag(
         }
         for (int q = tid; q < (t1 - t0) * tw16; q += NT) sym_flag_map[q] = make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();
-        sym_seg_walk<IP>(l, a0, nA, 4 * SPG_SYM_NQ * wv, 4 * SPG_SYM_NQ * W, gs, Gs, Aj, Bp, Bj16, sidx,
+        sym_seg_walk<IP>(l, a0, nA, 4 * SYM_NQ * wv, 4 * SYM_NQ * W, gs, Gs, Aj, Bp, Bj16, sidx,
                          [&](int c16) { flags[c16 - lo16] = (uint8_t)1; }, [](int) { return false; });
         __syncthreads();
         for (int t = wv; t < t1 - t0; t += W) {

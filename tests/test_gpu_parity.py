@@ -368,7 +368,7 @@ def _random_rows(rng, rows, cols, per_row):
 
 @pytest.mark.parametrize("ncols,choices", [(20000, [0, 40, 300, 700, 1500]), (140000, [0, 100, 300, 600, 900])])
 def test_symbolic_segments_long_and_ragged(ncols, choices):
-    """The segment symbolic kernel's round-6 loop (k_tile_sym_seg, SPG_SYM_PF): a round's first
+    """The segment symbolic kernel's round-6 loop (k_tile_sym_seg, SYM_PF): a round's first
     three steps of column loads together, the next round's extents as raw words a round later,
     then the extra steps of segments longer than 384 columns.  B rows of 0 to 1500 entries,
     A rows whose entry counts are not multiples of 16, an empty A row; whole-row symbolic tiles
