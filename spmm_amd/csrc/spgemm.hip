@@ -1836,7 +1836,8 @@ spg_status_t spg_symbolic(spg_handle_t h, spg_plan_t p, void* C_indptr, spg_inde
     }
     // the row-pointer scan mirrors the control words (+ every chunk's spill count) into the
     // pinned buffer: no device->host copy
-    const bool chunks = p->nspc > 0 && !p->counts_ready;
+    const bool counted = !p->counts_ready;   // this call ran the count pass
+    const bool chunks = p->nspc > 0 && counted;
     const int nread = chunks ? 16 + p->nspc : 5;
     st = C_indptr_type == SPG_INDEX_64I ? run_scan<int64_t>(h, *p, C_indptr, nread)
                                         : run_scan<int32_t>(h, *p, C_indptr, nread);
@@ -1851,8 +1852,11 @@ spg_status_t spg_symbolic(spg_handle_t h, spg_plan_t p, void* C_indptr, spg_inde
         for (auto& v : p->chunk_spills) v &= 0xffffffffLL;
     }
     // the short-row kernel spills the same rows in both passes: none in the symbolic pass
-    // (one launch over all rows) means the numeric spill launch can be skipped
-    if (p->use_short && (p->alg == SPG_ALG2 || fused_alg1(*p))) p->sym_spills = (int64_t)(uint32_t)(sc[4] & 0xffffffffu);
+    // (one launch over all rows) means the numeric spill launch can be skipped.  Only a call that
+    // ran the count pass reads that count: on a repeated call the word may have been cleared for
+    // the numeric pass (ALG1's single pass that outgrew its estimate set sym_spills itself)
+    if (counted && p->use_short && (p->alg == SPG_ALG2 || fused_alg1(*p)))
+        p->sym_spills = (int64_t)(uint32_t)(sc[4] & 0xffffffffu);
     p->counts_ready = true;      // counts stay valid for a repeated call
     if (sc[1]) return SPG_STATUS_OVERFLOW;
     p->nnzC = sc[0];

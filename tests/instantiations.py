@@ -4,6 +4,13 @@ tests/test_instantiations_cpu.py and tests/test_gpu_instantiations.py.
 
 A plain helper module (no pytest hooks).  Everything is generated from seeds.
 
+The C-ABI driver (run_abi, run_ws, run_tiles) hands the library poisoned, guarded buffers
+(tests/guarded.py) for everything it writes -- the workspace at exactly its queried size and C's
+three arrays -- checks the guard bands after the final synchronize and compares A's and B's device
+arrays with what was uploaded; run_poisoned is the per-case schedule of
+tests/test_gpu_poisoned_products.py (both poisons, repeated spg_symbolic, a stale shared
+workspace, ALG1's workspace hand-off, spg_spgemm_ws).
+
 What the other parity tests leave out: they reach most kernels with random matrices of int32 row
 pointers and moderate row lengths.  Here every case runs with A/B row pointers (IP) and C row
 pointers (CP) of both widths -- the C ABI lets the caller choose C's, where the Python shim picks
@@ -608,11 +615,25 @@ class Uploaded:
     def __init__(self, M, device="cuda:0"):
         import torch
         self.shape, self.nnz, self.dtype = M.shape, M.nnz, M.dtype
-        self.indptr = {32: torch.from_numpy(M.indptr.astype(np.int32)).to(device),
-                       64: torch.from_numpy(M.indptr.astype(np.int64)).to(device)}
-        self.indices = torch.from_numpy(M.indices.astype(np.int32)).to(device)
-        self.data = torch.from_numpy(np.array(M.data)).to(device)
+        host = {"indptr32": M.indptr.astype(np.int32), "indptr64": M.indptr.astype(np.int64),
+                "indices": M.indices.astype(np.int32), "values": np.array(M.data)}
+        up = {k: torch.from_numpy(v).to(device) for k, v in host.items()}
+        self.indptr = {32: up["indptr32"], 64: up["indptr64"]}
+        self.indices, self.data = up["indices"], up["values"]
         self.device = device
+        # a second upload of the same host arrays, never handed to the library
+        self._arrays = up
+        self._uploaded = {k: torch.from_numpy(v).to(device) for k, v in host.items()}
+
+    def check_unchanged(self, what=""):
+        """The device arrays handed to the library (row pointer in both widths, indices, values)
+        are byte for byte what was uploaded."""
+        import torch
+        names = list(self._arrays)
+        same = torch.stack([(self._arrays[k].view(torch.uint8) == self._uploaded[k].view(torch.uint8)).all()
+                            for k in names]).cpu()       # (one synchronise for the four arrays)
+        bad = [k for k, ok in zip(names, same.tolist()) if not ok]
+        assert not bad, f"{what}: input arrays {bad} were written"
 
     def view(self, ip):
         from spmm_amd._lib import SpgCsr
@@ -621,13 +642,44 @@ class Uploaded:
                       self.data.data_ptr(), ip, vt)
 
 
-def run_abi(A, B, alg, alpha=1.0, cf=CF, ip=32, cp=32, env=None, info=None):
+def _scalar(dtype, v):
+    """One host value of a value type for the C ABI (a (re, im) pair if complex)."""
+    ct = ctypes.c_float if np.dtype(dtype).type in (np.float32, np.complex64) else ctypes.c_double
+    if np.dtype(dtype).kind == "c":
+        return (ct * 2)(complex(v).real, complex(v).imag)
+    return ct(float(v))
+
+
+def _in_workspace(ws, ptr, nbytes, dtype, what):
+    """The `nbytes` at device address `ptr` as a tensor: a view of the guarded workspace `ws`,
+    which must hold all of them inside its interior."""
+    off = ptr - ws.data_ptr()
+    assert 0 <= off and off + nbytes <= ws.nbytes, f"{what}: [{off}, {off + nbytes}) outside the {ws.nbytes}-byte workspace"
+    return ws.bytes()[off:off + nbytes].view(dtype)
+
+
+def run_abi(A, B, alg, alpha=1.0, cf=CF, ip=32, cp=32, env=None, info=None, fill=0xFF, ws=None, first_cp=None,
+            in_place=False, extra=None):
     """C = alpha * A.B through spg_plan -> spg_symbolic -> spg_numeric with row pointers of `ip`
     bits for A and B and `cp` bits for C.  A, B: scipy CSR matrices or Uploaded.  alg 1, 2, 3 or
     "3c" (ALG3 with its chunks kept: SPG_ALG3_CHUNK_ALWAYS).  Returns (indptr, indices, data) as
-    numpy arrays, indptr in the width asked for; `info` (a dict) receives the plan's plan_info."""
+    numpy arrays, indptr in the width asked for; `info` (a dict) receives the plan's plan_info.
+
+    The workspace (exactly the queried size), C's row pointer, C's indices and C's values are
+    guarded buffers (tests/guarded.py) poisoned with the byte `fill`: an entry the kernels leave
+    unwritten keeps the poison, and all four guards are checked after the final synchronize, as
+    are A's and B's device arrays against what was uploaded.
+      ws: a guarded workspace to run in as it stands (at least the queried size; never refilled
+        here) instead of a fresh one.
+      first_cp: call spg_symbolic with a guarded row pointer of that width first, then again with
+        `cp` (the header's repeated call); extra["first"] = (that row pointer, its nnzC).
+      in_place: C's indices and values are the workspace views spg_result_in_workspace names
+        (which must exist): spg_numeric only scales.
+      extra (a dict) also receives "in_workspace" (spg_result_in_workspace returned pointers),
+        "nnz" and "workspace_bytes"."""
     import torch
     from spmm_amd import _lib
+    from tests.guarded import guarded
     dA = A if isinstance(A, Uploaded) else Uploaded(A)
     dB = B if isinstance(B, Uploaded) else Uploaded(B)
     dev = dA.device
@@ -645,11 +697,16 @@ def run_abi(A, B, alg, alpha=1.0, cf=CF, ip=32, cp=32, env=None, info=None):
     al = (ct * 2)(complex(alpha).real, complex(alpha).imag) if cplx else ct(float(alpha))
     tdt = {np.float32: torch.float32, np.float64: torch.float64, np.complex64: torch.complex64,
            np.complex128: torch.complex128}[dA.dtype.type]
+    what = f"alg={alg} IP={ip} CP={cp} fill={fill:#04x}"
+    extra = {} if extra is None else extra
     with environ(env):
         wsb = ctypes.c_size_t(0)
         _lib.check(lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ctypes.byref(wsb), None, None),
                    "spg_plan")
-        ws = torch.empty(max(wsb.value, 1), dtype=torch.uint8, device=dev)
+        if ws is None:      # the queried size, not a byte more
+            ws = guarded(wsb.value, "uint8", fill, dev, "workspace")
+        assert ws.nbytes >= wsb.value, (ws.nbytes, wsb.value)
+        extra["workspace_bytes"] = wsb.value
         plan = ctypes.c_void_p()
         _lib.check(lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ctypes.byref(wsb),
                                 ctypes.c_void_p(ws.data_ptr()), ctypes.byref(plan)), "spg_plan")
@@ -663,19 +720,46 @@ def run_abi(A, B, alg, alpha=1.0, cf=CF, ip=32, cp=32, env=None, info=None):
                              "tiles_per_row": pi.tiles_per_row, "dense_tiles": bool(pi.dense_tiles),
                              "lds_ordered": bool(pi.lds_ordered), "record_group": int(pi.record_group),
                              "chunk_rows": [int(x) for x in rows]})
-            indptr = torch.empty(m + 1, dtype=torch.int32 if cp == 32 else torch.int64, device=dev)
             nnz = ctypes.c_int64(0)
+            first = None
+            if first_cp is not None:
+                first = guarded(m + 1, f"int{first_cp}", fill, dev, "C.indptr (first spg_symbolic)")
+                _lib.check(lib.spg_symbolic(h.ptr, plan, ctypes.c_void_p(first.data_ptr()), first_cp,
+                                            ctypes.byref(nnz)), "spg_symbolic")
+                first_nnz = int(nnz.value)
+                nnz = ctypes.c_int64(0)
+            indptr = guarded(m + 1, f"int{cp}", fill, dev, "C.indptr")
             _lib.check(lib.spg_symbolic(h.ptr, plan, ctypes.c_void_p(indptr.data_ptr()), cp, ctypes.byref(nnz)),
                        "spg_symbolic")
             nz = int(nnz.value)
-            cj = torch.empty(max(nz, 1), dtype=torch.int32, device=dev)
-            cx = torch.empty(max(nz, 1), dtype=tdt, device=dev)
-            vc = _lib.SpgCsr(m, n, nz, indptr.data_ptr(), cj.data_ptr(), cx.data_ptr(), cp, va.value_type)
+            pj, px = ctypes.c_void_p(), ctypes.c_void_p()
+            _lib.check(lib.spg_result_in_workspace(plan, ctypes.byref(pj), ctypes.byref(px)), "spg_result_in_workspace")
+            assert bool(pj.value) == bool(px.value)
+            extra["in_workspace"], extra["nnz"] = bool(pj.value), nz
+            gj = gx = None
+            if in_place:
+                assert pj.value and px.value, f"{what}: C is not in the workspace"
+                cj = _in_workspace(ws, pj.value, 4 * nz, torch.int32, what + " C.indices")
+                cx = _in_workspace(ws, px.value, np.dtype(dA.dtype).itemsize * nz, tdt, what + " C.values")
+                jp, xp = pj.value, px.value
+            else:
+                gj = guarded(nz, "int32", fill, dev, "C.indices")
+                gx = guarded(nz, dA.dtype, fill, dev, "C.values")
+                cj, cx, jp, xp = gj.t, gx.t, gj.data_ptr(), gx.data_ptr()
+            vc = _lib.SpgCsr(m, n, nz, indptr.data_ptr(), jp, xp, cp, va.value_type)
             _lib.check(lib.spg_numeric(h.ptr, plan, ctypes.byref(al), ctypes.byref(vc)), "spg_numeric")
             torch.cuda.synchronize()
         finally:
             lib.spg_plan_destroy(plan)
-    return indptr.cpu().numpy(), cj[:nz].cpu().numpy(), cx[:nz].cpu().numpy()
+    out = indptr.t.cpu().numpy(), cj.cpu().numpy(), cx.cpu().numpy()
+    for g in (ws, indptr, first, gj, gx):
+        if g is not None:
+            g.check(f"{what} {g.name}")
+    dA.check_unchanged(what + " A")
+    dB.check_unchanged(what + " B")
+    if first is not None:
+        extra["first"] = (first.t.cpu().numpy(), first_nnz)
+    return out
 
 
 def run_python(A, B, alg=2, alpha=1.0):
@@ -688,6 +772,296 @@ def run_python(A, B, alg=2, alpha=1.0):
     C = cusparse.spgemm(dA, dB, alpha=alpha, alg=alg)
     torch.cuda.synchronize()
     return C.indptr.cpu().numpy(), C.indices.cpu().numpy(), C.data.cpu().numpy()
+
+
+def _handle_views(A, B, ip):
+    import torch
+    from spmm_amd import _lib
+    dA = A if isinstance(A, Uploaded) else Uploaded(A)
+    dB = B if isinstance(B, Uploaded) else Uploaded(B)
+    h = _lib.get_handle(torch.device(dA.device).index or 0)
+    h.set_stream(torch.cuda.current_stream().cuda_stream)
+    return dA, dB, h, dA.view(ip), dB.view(ip)
+
+
+def workspace_bytes(A, B, alg, cf=CF, ip=32, env=None):
+    """spg_plan's size query."""
+    from spmm_amd import _lib
+    dA, dB, h, va, vb = _handle_views(A, B, ip)
+    env = dict(env or {})
+    if alg == "3c":
+        env["SPG_ALG3_CHUNK_ALWAYS"] = "1"
+    wsb = ctypes.c_size_t(0)
+    with environ(env):
+        _lib.check(h.lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), 3 if alg == "3c" else int(alg), cf,
+                                  ctypes.byref(wsb), None, None), "spg_plan")
+    return int(wsb.value)
+
+
+def run_ws(A, B, alg, alpha=1.0, cf=CF, ip=32, cp=32, env=None, fill=0xFF):
+    """C = alpha * A.B through spg_spgemm_ws on a guarded workspace of the queried size and a
+    guarded row pointer: C in the workspace (ALG1 single pass: views of it, which must lie inside
+    it) or, with the live plan the call returns, spg_numeric into guarded arrays.  Returns
+    (indptr, indices, data), in_workspace."""
+    import torch
+    from spmm_amd import _lib
+    from tests.guarded import guarded
+    dA, dB, h, va, vb = _handle_views(A, B, ip)
+    lib, dev = h.lib, dA.device
+    m, n = dA.shape[0], dB.shape[1]
+    what = f"spg_spgemm_ws alg={alg} IP={ip} CP={cp} fill={fill:#04x}"
+    al = _scalar(dA.dtype, alpha)
+    tdt = guarded(0, dA.dtype).t.dtype
+    with environ(dict(env or {})):
+        ws = guarded(workspace_bytes(dA, dB, alg, cf, ip, env), "uint8", fill, dev, "workspace")
+        indptr = guarded(m + 1, f"int{cp}", fill, dev, "C.indptr")
+        nnz, peak = ctypes.c_int64(0), ctypes.c_size_t(0)
+        pj, px, plan = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        _lib.check(lib.spg_spgemm_ws(h.ptr, ctypes.byref(va), ctypes.byref(vb), int(alg), cf, ctypes.byref(al),
+                                     ctypes.c_void_p(ws.data_ptr()), ws.nbytes, ctypes.c_void_p(indptr.data_ptr()), cp,
+                                     ctypes.byref(nnz), ctypes.byref(pj), ctypes.byref(px), ctypes.byref(peak),
+                                     ctypes.byref(plan)), "spg_spgemm_ws")
+        nz = int(nnz.value)
+        gj = gx = None
+        if plan.value:
+            assert not pj.value and not px.value
+            try:
+                gj = guarded(nz, "int32", fill, dev, "C.indices")
+                gx = guarded(nz, dA.dtype, fill, dev, "C.values")
+                vc = _lib.SpgCsr(m, n, nz, indptr.data_ptr(), gj.data_ptr(), gx.data_ptr(), cp, va.value_type)
+                _lib.check(lib.spg_numeric(h.ptr, plan, ctypes.byref(al), ctypes.byref(vc)), "spg_numeric")
+                torch.cuda.synchronize()
+            finally:
+                lib.spg_plan_destroy(plan)
+            cj, cx = gj.t, gx.t
+        else:
+            assert nz == 0 or (pj.value and px.value), what
+            torch.cuda.synchronize()
+            cj = (_in_workspace(ws, pj.value, 4 * nz, torch.int32, what + " C.indices") if nz
+                  else torch.empty(0, dtype=torch.int32, device=dev))
+            cx = (_in_workspace(ws, px.value, np.dtype(dA.dtype).itemsize * nz, tdt, what + " C.values") if nz
+                  else torch.empty(0, dtype=tdt, device=dev))
+    out = indptr.t.cpu().numpy(), cj.cpu().numpy(), cx.cpu().numpy()
+    for g in (ws, indptr, gj, gx):
+        if g is not None:
+            g.check(f"{what} {g.name}")
+    dA.check_unchanged(what + " A")
+    dB.check_unchanged(what + " B")
+    return out, not plan.value
+
+
+def tile_groupings(tiles):
+    """The value-tile ranges of every way spg_numeric_tiles is driven here: one range per tile,
+    two groups, all tiles in one call -- each in ascending and in descending tile order."""
+    if tiles == 1:       # (a single value tile: every grouping is the one call)
+        return [("all/ascending", [(0, 1)])]
+    per_tile = [(t, t + 1) for t in range(tiles)]
+    two = [(0, tiles // 2), (tiles // 2, tiles)]
+    return [("per-tile/ascending", per_tile), ("per-tile/descending", per_tile[::-1]), ("two/ascending", two),
+            ("two/descending", two[::-1]), ("all/ascending", [(0, tiles)])]
+
+
+def run_tiles(A, B, alpha=1.0, ip=32, cp=32, env=None, fill=0xFF):
+    """The numeric phase by value tiles through the C ABI: one ALG2 plan, spg_tile_values into a
+    guarded nnz(B) buffer, spg_symbolic, then for every grouping of tile_groupings() a fresh
+    poisoned guarded C filled by spg_numeric_tiles calls.  Returns {grouping: (indptr, indices,
+    data)}, {grouping: [poisoned entries of C left after each call]} and the value-tile count."""
+    import torch
+    from spmm_amd import _lib
+    from tests.guarded import guarded
+    assert fill == 0xFF      # the poison must be told from a result: index -1, NaN value
+    real_t = torch.float32 if np.dtype(A.dtype) in (np.float32, np.complex64) else torch.float64
+    dA, dB, h, va, vb = _handle_views(A, B, ip)
+    lib, dev = h.lib, dA.device
+    m, n = dA.shape[0], dB.shape[1]
+    al = _scalar(dA.dtype, alpha)
+    results, left = {}, {}
+    with environ(dict(env or {})):
+        ws = guarded(workspace_bytes(dA, dB, 2, CF, ip, env), "uint8", fill, dev, "workspace")
+        wsb = ctypes.c_size_t(ws.nbytes)
+        plan = ctypes.c_void_p()
+        _lib.check(lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), 2, CF, ctypes.byref(wsb),
+                                ctypes.c_void_p(ws.data_ptr()), ctypes.byref(plan)), "spg_plan")
+        try:
+            pi = _lib.SpgPlanInfo()
+            _lib.check(lib.spg_plan_info(plan, ctypes.byref(pi), None, 0), "spg_plan_info")
+            assert pi.path == 2 and pi.n_chunks == 1, (pi.path, pi.n_chunks)
+            tiles = -(-pi.tiles_per_row // pi.record_group)
+            offs = (ctypes.c_int64 * (tiles + 1))()
+            _lib.check(lib.spg_tile_value_offsets(h.ptr, plan, offs, tiles + 1), "spg_tile_value_offsets")
+            assert offs[0] == 0 and offs[tiles] == dB.nnz, list(offs)
+            tm = guarded(dB.nnz, dA.dtype, fill, dev, "tile-major values")
+            _lib.check(lib.spg_tile_values(h.ptr, plan, ctypes.c_void_p(tm.data_ptr())), "spg_tile_values")
+            indptr = guarded(m + 1, f"int{cp}", fill, dev, "C.indptr")
+            nnz = ctypes.c_int64(0)
+            _lib.check(lib.spg_symbolic(h.ptr, plan, ctypes.c_void_p(indptr.data_ptr()), cp, ctypes.byref(nnz)),
+                       "spg_symbolic")
+            nz = int(nnz.value)
+            for name, ranges in tile_groupings(tiles):
+                what = f"spg_numeric_tiles {name} IP={ip} CP={cp}"
+                gj = guarded(nz, "int32", fill, dev, "C.indices")
+                gx = guarded(nz, dA.dtype, fill, dev, "C.values")
+                vc = _lib.SpgCsr(m, n, nz, indptr.data_ptr(), gj.data_ptr(), gx.data_ptr(), cp, va.value_type)
+                left[name] = []
+                for t0, t1 in ranges:
+                    _lib.check(lib.spg_numeric_tiles(h.ptr, plan, ctypes.byref(al), ctypes.byref(vc),
+                                                     ctypes.c_void_p(tm.data_ptr()), t0, t1), "spg_numeric_tiles")
+                    torch.cuda.synchronize()
+                    left[name].append(int(((gj.t == -1) | torch.isnan(gx.t.view(real_t).view(nz, -1)).any(1)).sum()))
+                results[name] = indptr.t.cpu().numpy(), gj.t.cpu().numpy(), gx.t.cpu().numpy()
+                for g in (ws, indptr, tm, gj, gx):
+                    g.check(f"{what} {g.name}")
+        finally:
+            lib.spg_plan_destroy(plan)
+    dA.check_unchanged("spg_numeric_tiles A")
+    dB.check_unchanged("spg_numeric_tiles B")
+    return results, left, tiles
+
+
+# ---------------------------------------------------------------------------------------------
+# Two inputs outside the case table: ALG1's single pass giving up (tests/test_gpu_parity.py and
+# tests/test_gpu_poisoned_products.py share them).
+
+@functools.lru_cache(maxsize=1)
+def estimate_overflow_pair():
+    """(A, B): A's entries select B's ten longest rows, so C outgrows the size ALG1's single pass
+    estimates from the expected product count, and the product is redone two-phase."""
+    rng = np.random.default_rng(43)
+    B = sp.random(2000, 3000, density=0.001, format="lil", random_state=rng)
+    for r in range(10):
+        B[r, rng.choice(3000, 1500, replace=False)] = rng.standard_normal(1500)
+    B = sp.csr_matrix(B)
+    rows, cols = [], []
+    for i in range(3000):
+        for c in rng.choice(10, 5, replace=False):
+            rows.append(i); cols.append(c)
+    A = sp.csr_matrix((rng.standard_normal(len(rows)), (rows, cols)), shape=(3000, 2000))
+    for M in (A, B):
+        M.sum_duplicates(); M.sort_indices()
+    return A, B
+
+
+@functools.lru_cache(maxsize=1)
+def long_row_pair():
+    """(A, B): a short-row shape with one A row of 300 entries, more than the 64 the single pass
+    takes: the pass hands over to the two-phase path."""
+    rng = np.random.default_rng(41)
+    A = sp.random(3000, 2000, density=0.004, format="lil", random_state=rng)
+    A[1234, :300] = rng.standard_normal(300)
+    A = sp.csr_matrix(A)
+    B = sp.random(2000, 3000, density=0.004, format="csr", random_state=rng)
+    A.sort_indices(); B.sort_indices()
+    return A, B
+
+
+def alg1_estimate(A, B):
+    """The entries ALG1's single pass sizes its output for (spg_plan, restated)."""
+    return int(min(1.15 * A.nnz * (B.nnz / B.shape[0]) + 4096.0, float(A.shape[0]) * float(B.shape[1])))
+
+
+COLS16_WIDTHS = (65535, 65536, 65537, 140000)     # 1, 1, 2 and 3 blocks of 65536 columns
+# rows cols16_matrix places by hand: label -> row
+COLS16_ROWS = {"empty": 0, "last-block": 1, "first-block": 2, "edges": 3, "last-column": 4, "all-blocks": 5,
+               "empty2": 6}
+
+
+@functools.lru_cache(maxsize=None)
+def cols16_matrix(cols):
+    """Canonical CSR for spg_cols16_split / spg_cols16_join, rows on the 65536-column blocks: an
+    empty row, a row only in the last block, one only in the first, one entry on each side of
+    every block edge, the last column alone, a row through every block, 300 random rows of 0..29,
+    then column 0 alone and a short row in the last block."""
+    rng = np.random.default_rng(seed_of("cols16", cols))
+    nb = (cols + 65535) // 65536
+    last0 = (nb - 1) * 65536
+    last = lambda m: np.sort(rng.choice(np.arange(last0, cols), min(m, cols - last0), replace=False))
+    edges = sorted({c for b in range(nb) for c in (b * 65536, min(cols, (b + 1) * 65536) - 1)})
+    rows = [[], last(40), np.arange(0, 50), edges, [cols - 1], np.sort(rng.choice(cols, 700, replace=False)), []]
+    rows += [np.sort(rng.choice(cols, int(rng.integers(0, 30)), replace=False)) for _ in range(300)]
+    rows += [[0], last(3)]
+    lens = np.array([len(r) for r in rows])
+    indptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    indices = np.concatenate([np.asarray(r, dtype=np.int32) for r in rows]).astype(np.int32)
+    M = sp.csr_matrix((np.ones(len(indices)), indices, indptr), shape=(len(rows), cols))
+    for a in (M.data, M.indices, M.indptr):
+        a.setflags(write=False)
+    return M
+
+
+def cols16_split_host(M):
+    """include/spgemm.h's 16-bit column format restated: (block_starts, lo16).  block_starts is
+    rows x (ceil(cols / 65536) - 1) uint32, per row the offset from the row's start of its first
+    entry with column >= c * 65536 (the row's length if there is none), c = 1, 2, ...; lo16 the
+    low 16 bits of every column."""
+    rows, cols = M.shape
+    nb1 = max(0, (cols + 65535) // 65536 - 1)
+    starts = np.zeros((rows, nb1), dtype=np.uint32)
+    for r in range(rows):
+        rc = M.indices[M.indptr[r]:M.indptr[r + 1]]
+        starts[r] = [np.searchsorted(rc, (b + 1) * 65536) for b in range(nb1)]
+    return starts, (M.indices & 0xFFFF).astype(np.uint16)
+
+
+def cols16_join_host(M, starts, lo16):
+    """The columns back from the split: an entry's high half is the number of block starts at or
+    below its offset in the row."""
+    out = np.empty(M.nnz, dtype=np.int32)
+    for r in range(M.shape[0]):
+        a, b = M.indptr[r], M.indptr[r + 1]
+        hi = (starts[r][None, :] <= np.arange(b - a)[:, None]).sum(axis=1) if starts.shape[1] else np.zeros(b - a, int)
+        out[a:b] = (hi.astype(np.int64) << 16) | lo16[a:b]
+    return out
+
+
+POISON_FILLS = (0x00, 0xFF)
+POISON_WIDTHS = ((32, 64), (64, 32))
+STALE_ORDER = (1, 2, "3c", 2)
+_NONE = np.zeros(0, dtype=np.int32)
+
+
+def run_poisoned(case):
+    """Every product of a case on poisoned, guarded buffers (tests/test_gpu_poisoned_products.py):
+    {key: (indptr, indices, data)}.  Keys:
+      "fill/<alg>/<fill>"    both poisons under every algorithm, (IP, CP) alternating between
+                             (32, 64) and (64, 32) so that both widths see both poisons;
+      "resym/<alg>"          spg_symbolic into an int32 row pointer, again into an int64 one, then
+                             spg_numeric; "resym-first/<alg>" holds the first row pointer and, as
+                             `indices`, the two nnzC;
+      "stale/<i>/<alg>"      ALG1, ALG2, "3c", ALG2 in ONE workspace sized for the largest query,
+                             poisoned once and never refilled; fresh plan and C arrays each;
+      "handoff/copy", "handoff/inplace"   ALG1 with alpha != 1 into guarded C arrays and, where
+                             spg_result_in_workspace names them, in the workspace views;
+      "ws/1", "ws/2"         spg_spgemm_ws, alpha != 1; "flags" holds as `indices`
+                             [handoff in workspace, ws/1 in workspace, ws/2 in workspace]."""
+    from tests.guarded import guarded
+    c = CASE[case]
+    A, B, _ = inputs(case)
+    dA, dB = Uploaded(A), Uploaded(B)
+    al = alpha_of(c.dname)
+    out = {}
+    for ai, alg in enumerate(ALGS):
+        for fi, fill in enumerate(POISON_FILLS):
+            ip, cp = POISON_WIDTHS[(ai + fi) % 2]
+            out[f"fill/{alg}/{fill:#04x}"] = run_abi(dA, dB, alg, 1.0, CF, ip, cp, c.env, fill=fill)
+    for alg in ALGS:
+        ex = {}
+        out[f"resym/{alg}"] = run_abi(dA, dB, alg, 1.0, CF, 32, 64, c.env, first_cp=32, extra=ex)
+        out[f"resym-first/{alg}"] = (ex["first"][0], np.array([ex["first"][1], ex["nnz"]], dtype=np.int64), _NONE)
+    size = max(workspace_bytes(dA, dB, alg, CF, 32, c.env) for alg in ALGS)
+    ws = guarded(size, "uint8", 0xFF, dA.device, "workspace (shared, never refilled)")
+    for i, alg in enumerate(STALE_ORDER):
+        out[f"stale/{i}/{alg}"] = run_abi(dA, dB, alg, 1.0, CF, 32, 32, c.env, ws=ws)
+    ex = {}
+    out["handoff/copy"] = run_abi(dA, dB, 1, al, CF, 64, 64, c.env, extra=ex)
+    if ex["in_workspace"]:
+        out["handoff/inplace"] = run_abi(dA, dB, 1, al, CF, 64, 64, c.env, in_place=True, fill=0x00)
+    flags = [int(ex["in_workspace"])]
+    for alg in (1, 2):
+        out[f"ws/{alg}"], inws = run_ws(dA, dB, alg, al, CF, 32, 64 if alg == 1 else 32, c.env,
+                                        fill=0xFF if alg == 1 else 0x00)
+        flags.append(int(inws))
+    out["flags"] = (_NONE, np.array(flags, dtype=np.int64), _NONE)
+    return out
 
 
 def run_cross(case):
@@ -708,10 +1082,11 @@ def run_cross(case):
     return out, infos
 
 
-def child_main(case, path):
-    """run_cross in a fresh process (a switch read once per process), results to an .npz."""
+def child_main(case, path, mode="cross"):
+    """run_cross (mode "cross") or run_poisoned (mode "poisoned") in a fresh process (a switch
+    read once per process), results to an .npz."""
     import json
-    out, infos = run_cross(case)
+    out, infos = run_cross(case) if mode == "cross" else (run_poisoned(case), {})
     arrs = {}
     for key, (p, j, x) in out.items():
         s = key if isinstance(key, str) else "|".join(str(v) for v in key)

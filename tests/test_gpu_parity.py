@@ -12,6 +12,7 @@ import pytest
 import scipy.sparse as sp
 
 from oracle import oracle
+from tests import instantiations as inst
 from tests.golden_cases import case_names, load
 
 torch = pytest.importorskip("torch")
@@ -485,12 +486,7 @@ def test_tile_path_dense_tiles_fp32_int64():
 def test_alg1_single_pass_fallback_long_row():
     """ALG1 runs as one fused pass for short-row shapes; a row with more than 64 entries
     makes the pass hand over to the upper-bound path, with the same result."""
-    rng = np.random.default_rng(41)
-    A = sp.random(3000, 2000, density=0.004, format="lil", random_state=rng)
-    A[1234, :300] = rng.standard_normal(300)
-    A = sp.csr_matrix(A)
-    B = sp.random(2000, 3000, density=0.004, format="csr", random_state=rng)
-    A.sort_indices(); B.sort_indices()
+    A, B = inst.long_row_pair()
     ref = oracle.spgemm(A, B, alpha=2.5, keep_zeros=True, sort=True)
     _assert_same(_gpu(A, B, alg=1, alpha=2.5), ref)
     _assert_same(_gpu(A, B, alg=2, alpha=2.5), ref)
@@ -560,18 +556,7 @@ def test_alg1_single_pass_estimate_overflow():
     """ALG1's single pass sizes its output from the expected product count; when A's
     entries select B's longest rows, the output outgrows the estimate and the product is
     redone two-phase, with the same bits."""
-    rng = np.random.default_rng(43)
-    B = sp.random(2000, 3000, density=0.001, format="lil", random_state=rng)
-    for r in range(10):
-        B[r, rng.choice(3000, 1500, replace=False)] = rng.standard_normal(1500)
-    B = sp.csr_matrix(B)
-    rows, cols = [], []
-    for i in range(3000):
-        for c in rng.choice(10, 5, replace=False):
-            rows.append(i); cols.append(c)
-    A = sp.csr_matrix((rng.standard_normal(len(rows)), (rows, cols)), shape=(3000, 2000))
-    for M in (A, B):
-        M.sum_duplicates(); M.sort_indices()
+    A, B = inst.estimate_overflow_pair()
     ref = oracle.spgemm(A, B, alpha=1.5, keep_zeros=True, sort=True)
     assert len(ref[1]) > 10 * A.nnz * (B.nnz / B.shape[0])
     _assert_same(_gpu(A, B, alg=1, alpha=1.5), ref)
