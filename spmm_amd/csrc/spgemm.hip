@@ -164,6 +164,40 @@ spg_status_t dispatch_value(spg_dtype_t t, F&& f) {
     return SPG_STATUS_NOT_SUPPORTED;
 }
 
+// Runs f(IP{}) with IP the C++ type of row-pointer width t (check_csr admits only the two).
+template <typename F>
+spg_status_t dispatch_index(spg_index_t t, F&& f) {
+    return t == SPG_INDEX_64I ? f(int64_t{}) : f(int32_t{});
+}
+// f(IP{}, CP{}): the operands' row-pointer type and C's
+template <typename F>
+spg_status_t dispatch_index(spg_index_t ip, spg_index_t cp, F&& f) {
+    return dispatch_index(ip, [&](auto i) { return dispatch_index(cp, [&](auto c) { return f(i, c); }); });
+}
+inline size_t index_bytes(spg_index_t t) { return t == SPG_INDEX_64I ? 8 : 4; }
+
+// Workspace carving.  A cursor over offsets from the workspace's base: take(bytes) returns the
+// current offset and advances to the next 256-byte boundary.
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off += align_up(bytes);
+        return at;
+    }
+};
+// the 256-byte aligned base of a caller's workspace (the newer entry points ask for 256 bytes
+// of slack instead of an aligned pointer)
+inline char* ws_base(void* workspace) { return (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
+// The two-call convention of the entry points that take a workspace: without one the call is a
+// size query (*bytes = total); with one, *bytes must reach total.  True when the call ends
+// here, with `st`.
+inline bool size_query(size_t total, size_t* bytes, const void* workspace, spg_status_t& st) {
+    if (!workspace) *bytes = total;
+    st = workspace && *bytes < total ? SPG_STATUS_INVALID_VALUE : SPG_STATUS_SUCCESS;
+    return !workspace || st != SPG_STATUS_SUCCESS;
+}
+
 // SPG_SHORT_KERNEL=short selects the owner-round k_short for short rows (A/B timing);
 // the default is k_row.  Read once per process.
 inline bool row_kernel_enabled() {
@@ -177,6 +211,8 @@ inline bool row_kernel_enabled() {
 inline int64_t grid_for(int64_t rows, int per_block) { return (rows + per_block - 1) / per_block; }
 
 inline int64_t scan_tiles(int64_t n) { return n > 0 ? (n + SCAN_TILE - 1) / SCAN_TILE : 1; }
+// bytes of the status words of a look-back scan over n elements: a ticket + one word per tile
+inline size_t status_bytes(int64_t n) { return sizeof(unsigned long long) * (size_t)(scan_tiles(n) + 1); }
 // 64-row groups (ALG1 on k_row: one published prefix per group)
 inline int64_t row_groups(int64_t n) { return (n + WAVE - 1) / WAVE; }
 
@@ -456,8 +492,7 @@ spg_status_t launch_scan(spg_handle_t h, int64_t n, const IN* in, OUT* out,
                          int64_t* host_mirror = nullptr, int64_t mirror_gen = 0, int mirror_n = 0,
                          const int64_t* seed = nullptr) {
     const int64_t tiles = scan_tiles(n);
-    if (zero_status)
-        SPG_HIP(h, hipMemsetAsync(status, 0, sizeof(unsigned long long) * (size_t)(tiles + 1), h->stream));
+    if (zero_status) SPG_HIP(h, hipMemsetAsync(status, 0, status_bytes(n), h->stream));
     // (the handle's wait bound: SPG_LB_SPIN_TICKS=0 sends every look-back of an out-of-place
     // scan down its direct path, for the tests; in-place scans always wait, k_scan_lb)
     timed_launch(h, SPG_PHASE_SCAN, k_scan_lb<OUT, IN>, dim3((unsigned)tiles), dim3(BLOCK), n, in, out, status, scal,
@@ -484,8 +519,9 @@ spg_status_t launch_products(spg_handle_t h, const spg_csr_t& A, const spg_csr_t
 spg_status_t products_prefix(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B,
                              int64_t* cnt, int64_t* pref, int64_t* scal,
                              unsigned long long* status, bool zero_status = true) {
-    return A.indptr_type == SPG_INDEX_64I ? launch_products<int64_t>(h, A, B, cnt, pref, scal, status, zero_status)
-                                          : launch_products<int32_t>(h, A, B, cnt, pref, scal, status, zero_status);
+    return dispatch_index(A.indptr_type, [&](auto ip) {
+        return launch_products<decltype(ip)>(h, A, B, cnt, pref, scal, status, zero_status);
+    });
 }
 
 spg_status_t read_scalars(spg_handle_t h, const int64_t* dev, int n, int64_t* out);
@@ -499,12 +535,12 @@ spg_status_t products_total(spg_handle_t h, const spg_csr_t& A, const spg_csr_t&
     if (A.nnz > 0) {
         PhaseTimer pt(h, SPG_PHASE_PRODUCTS);
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(A.nnz, 4 * BLOCK), 256));
-        if (A.indptr_type == SPG_INDEX_64I)
-            hipLaunchKernelGGL(k_products_total<int64_t>, dim3(grid), dim3(BLOCK), 0, h->stream, A.nnz,
-                               (const int32_t*)A.indices, (const int64_t*)B.indptr, acc);
-        else
-            hipLaunchKernelGGL(k_products_total<int32_t>, dim3(grid), dim3(BLOCK), 0, h->stream, A.nnz,
-                               (const int32_t*)A.indices, (const int32_t*)B.indptr, acc);
+        dispatch_index(A.indptr_type, [&](auto ip) {
+            using IP = decltype(ip);
+            hipLaunchKernelGGL(k_products_total<IP>, dim3(grid), dim3(BLOCK), 0, h->stream, A.nnz,
+                               (const int32_t*)A.indices, (const IP*)B.indptr, acc);
+            return SPG_STATUS_SUCCESS;
+        });
         SPG_LAUNCHED(h);
     }
     return read_scalars(h, (const int64_t*)acc, 1, P);
@@ -649,6 +685,9 @@ inline int record_group_log2(const spg_plan_s& p) {
 inline bool fused_alg1(const spg_plan_s& p) {
     return p.alg == SPG_ALG1 && p.use_short && !p.use_tile && p.A.rows <= (1LL << 24);
 }
+// ALG1 otherwise, off the tile path: one structure + value pass at upper-bound offsets (the
+// product prefix p.ub) into the P-entry buffers tj/tx, compacted into C by spg_numeric
+inline bool alg1_upper_bound(const spg_plan_s& p) { return p.alg == SPG_ALG1 && !p.use_tile && !fused_alg1(p); }
 
 // status words: products scan | row-pointer scan | item scan + segment-table scan (tile path)
 inline size_t status_words(const spg_plan_s& p) {
@@ -656,6 +695,7 @@ inline size_t status_words(const spg_plan_s& p) {
            (p.use_tile ? (size_t)scan_tiles(tile_items(p)) + 1 + (size_t)scan_tiles(bt_entries(p)) + 1 : 0) +
            (fused_alg1(p) ? (size_t)std::max<int64_t>(grid_for(p.A.rows, ShortSmall::WPB), row_groups(p.A.rows)) + 1 : 0);
 }
+inline unsigned long long* rowptr_scan_status(const spg_plan_s& p) { return p.scan_status + scan_tiles(p.A.rows) + 1; }
 inline unsigned long long* item_scan_status(const spg_plan_s& p) {
     return p.scan_status + 2 * (scan_tiles(p.A.rows) + 1);
 }
@@ -663,41 +703,43 @@ inline unsigned long long* bt_scan_status(const spg_plan_s& p) {
     return item_scan_status(p) + scan_tiles(tile_items(p)) + 1;
 }
 
+// Offsets from the workspace pointer itself (spg_plan asks for no alignment slack).  The
+// max(.., 1) floors keep every region non-empty.
 Layout make_layout(const spg_plan_s& p) {
     Layout L;
-    size_t off = 0;
-    L.scalars = off; off = align_up(off + (16 + (size_t)p.nspc) * sizeof(int64_t));
-    L.status = off;  off = align_up(off + sizeof(unsigned long long) * status_words(p));
-    L.row_cnt = off; off = align_up(off + sizeof(int64_t) * (size_t)(p.A.rows + 1));
-    L.seg = off;     off = align_up(off + sizeof(uint32_t) * 2 * (size_t)std::max<int64_t>(p.seg_len, 1));
-    L.spill = off;   off = align_up(off + sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(p.A.rows, 1));
+    Carver c;
+    L.scalars = c.take((16 + (size_t)p.nspc) * sizeof(int64_t));
+    L.status = c.take(sizeof(unsigned long long) * status_words(p));
+    L.row_cnt = c.take(sizeof(int64_t) * (size_t)(p.A.rows + 1));
+    L.seg = c.take(sizeof(uint32_t) * 2 * (size_t)std::max<int64_t>(p.seg_len, 1));
+    L.spill = c.take(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(p.A.rows, 1));
     if (p.use_tile) {
-        L.tptr = off;  off = align_up(off + sizeof(int32_t) * (size_t)(bt_entries(p) + 1));
-        L.sidx = off;  off = align_up(off + sizeof(uint32_t) * (size_t)p.B.rows * (size_t)(sym_tiles(p) + 1));
+        L.tptr = c.take(sizeof(int32_t) * (size_t)(bt_entries(p) + 1));
+        L.sidx = c.take(sizeof(uint32_t) * (size_t)p.B.rows * (size_t)(sym_tiles(p) + 1));
         // (B's records, then the lean kernels' sentinel records)
-        L.brec = off;  off = align_up(off + brec_bytes(p.A.value_type) * (size_t)(p.B.nnz + SENT_REGIONS * SENT_N));
-        L.items = off; off = align_up(off + sizeof(int64_t) * (size_t)(tile_item_slots(p) + 1));
+        L.brec = c.take(brec_bytes(p.A.value_type) * (size_t)(p.B.nnz + SENT_REGIONS * SENT_N));
+        L.items = c.take(sizeof(int64_t) * (size_t)(tile_item_slots(p) + 1));
         // B's column indices modulo 65536 (the symbolic pass's columns: a symbolic tile never
         // crosses a 65536-aligned block)
-        L.bj16 = off;  off = align_up(off + sizeof(uint16_t) * (size_t)(p.B.nnz + 8));   // (+8: whole 16-byte loads)
+        L.bj16 = c.take(sizeof(uint16_t) * (size_t)(p.B.nnz + 8));   // (+8: whole 16-byte loads)
         // item bitmaps; before the first symbolic pass the region holds the row-major
         // boundary index the tile-major B is built from
         const size_t bm = tile_dense(p) ? 0 : sizeof(uint32_t) * (size_t)tile_items(p) * (size_t)((1 << p.tws) >> 5);
         const size_t ti = sizeof(uint2) * (size_t)p.B.rows * (size_t)tiles_padded(p);
-        L.bitmap = off; off = align_up(off + std::max(bm, ti));
+        L.bitmap = c.take(std::max(bm, ti));
     }
     if (p.alg == SPG_ALG1 && !p.use_tile) {
         // single pass: C itself, `cap` entries (an estimate); upper-bound path: P entries
-        const int64_t n = fused_alg1(p) ? p.cap : p.P;
-        if (!fused_alg1(p)) { L.ub = off; off = align_up(off + sizeof(int64_t) * (size_t)(p.A.rows + 1)); }
+        const size_t n = (size_t)std::max<int64_t>(fused_alg1(p) ? p.cap : p.P, 1);
+        if (!fused_alg1(p)) L.ub = c.take(sizeof(int64_t) * (size_t)(p.A.rows + 1));
         if (fused_alg1(p) && p.use_row) {
             const size_t eb = p.A.indptr_type == SPG_INDEX_64I ? sizeof(RowExt<int64_t>) : sizeof(RowExt<int32_t>);
-            L.ext = off; off = align_up(off + eb * (size_t)std::max<int64_t>(p.A.nnz, 1));
+            L.ext = c.take(eb * (size_t)std::max<int64_t>(p.A.nnz, 1));
         }
-        L.tj = off; off = align_up(off + sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1));
-        L.tx = off; off = align_up(off + vbytes(p.A.value_type) * (size_t)std::max<int64_t>(n, 1));
+        L.tj = c.take(sizeof(int32_t) * n);
+        L.tx = c.take(vbytes(p.A.value_type) * n);
     }
-    L.total = off;
+    L.total = c.off;
     return L;
 }
 
@@ -927,7 +969,7 @@ spg_status_t run_scan(spg_handle_t h, spg_plan_s& p, void* out, int mirror_n = 0
     // the row-pointer scan uses the second status region of the control block
     // (mirror_n > 0: the control words also go to the pinned buffer, for wait_mirror)
     return launch_scan<OUT>(h, p.A.rows, (const int64_t*)p.row_cnt, (OUT*)out,
-                            p.scan_status + scan_tiles(p.A.rows) + 1, p.scalars, false, nullptr, nullptr,
+                            rowptr_scan_status(p), p.scalars, false, nullptr, nullptr,
                             mirror_n ? h->pinned : nullptr, mirror_n ? ++h->mirror_gen : 0, mirror_n);
 }
 
@@ -1165,57 +1207,59 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
     return SPG_STATUS_SUCCESS;
 }
 
-// ALG1 single pass: structure + values + row pointer in one launch, compact into tj/tx
+// ALG1 single pass on k_row: structure + values + row pointer, compact into tj/tx
 template <typename T, typename IP, typename OUT>
-spg_status_t alg1_fused_run(spg_handle_t h, spg_plan_s& p, void* cp) {
-    if (p.use_row) {
-        // count pass (every row), row-pointer scan, one numeric pass into C's compact
-        // arrays (estimate-sized: a total past `cap` writes nothing and is redone)
-        // no memset of the control block: the count pass zeroes the scan's status words,
-        // spills are counted in the handle's counter, which the scan moves into
-        // scalars[5] and re-arms
-        const unsigned grid = (unsigned)grid_for(p.A.rows, RowSmall::WPB);
-        const unsigned grid_sym = (unsigned)grid_for(p.A.rows, RowSmall::WPB);
-        // the numeric launch's scan words: ticket + tile status, then the group prefixes
-        unsigned long long* status = p.scan_status + scan_tiles(p.A.rows) + 1;
-        const int64_t nscan = scan_tiles(p.A.rows);
-        const int64_t nstatus = nscan + 1 + row_groups(p.A.rows);
-        RowExt<IP>* ext = (RowExt<IP>*)p.ext;
-        RowScan<OUT> sa{nscan, (OUT*)cp, status, status + nscan + 1, p.scalars, nullptr, nullptr, nullptr, 0, 0,
-                        h->lb_spin};
-        if (!p.counts_ready) {
-            if (h->spill_ctr_dirty) SPG_HIP(h, hipMemsetAsync(h->spill_ctr, 0, sizeof(int32_t), h->stream));
-            h->spill_ctr_dirty = true;
-            timed_launch(h, SPG_PHASE_SYMBOLIC, k_row<double, IP, int64_t, ROW_SYM, RowSmall>, dim3(grid_sym), dim3(RowSmall::WPB * WAVE),
-                               (int64_t)0, p.A.rows, p.B.cols, (const IP*)p.A.indptr,
-                               (const int32_t*)p.A.indices, (const double*)nullptr, (const IP*)p.B.indptr,
-                               (const int32_t*)p.B.indices, (const double*)nullptr, (const int64_t*)nullptr,
-                               (int32_t*)nullptr, (double*)nullptr, 1.0, p.row_cnt, p.spill, h->spill_ctr,
-                               (int)ROW_COUNT_ALL, (int64_t)0, (const int64_t*)nullptr, status, nstatus,
-                               ext, RowScan<int64_t>{});
-            SPG_LAUNCHED(h);
-            // the scan blocks hand the spill count over (to scalars[5]), re-arm the counter and
-            // mirror total / overflow / spills into the pinned buffer
-            sa.move_cnt = h->spill_ctr;
-            sa.move_dst = p.scalars + 5;
-            sa.host_mirror = h->pinned;
-            sa.mirror_gen = ++h->mirror_gen;
-            sa.mirror_n = 2;   // words 0, 1 (+ 5: the move)
-            h->spill_ctr_dirty = false;
-        } else {   // repeated call: the first call already moved the spill count
-            SPG_HIP(h, hipMemsetAsync(status, 0, sizeof(unsigned long long) * (size_t)nstatus, h->stream));
-        }
-        KernelTimer kt(h, SPG_PHASE_NUMERIC);
-        hipExtLaunchKernelGGL((k_row<T, IP, OUT, ROW_LB, RowSmall>), dim3((unsigned)(nscan + grid)),
-                              dim3(RowSmall::WPB * WAVE), 0, h->stream, kt.a, kt.b, 0, (int64_t)0, p.A.rows, p.B.cols,
-                              (const IP*)p.A.indptr, (const int32_t*)p.A.indices, (const T*)p.A.values,
-                              (const IP*)p.B.indptr, (const int32_t*)p.B.indices, (const T*)p.B.values,
-                              (const OUT*)nullptr, p.tj, (T*)p.tx, (T)1, p.row_cnt, p.spill, spill_counts(p, true),
-                              (int)ROW_LISTED, std::max<int64_t>(p.cap, 1), (const int64_t*)nullptr,
-                              (unsigned long long*)nullptr, (int64_t)0, ext, sa);
+spg_status_t alg1_row_launch(spg_handle_t h, spg_plan_s& p, void* cp) {
+    // count pass (every row), row-pointer scan, one numeric pass into C's compact
+    // arrays (estimate-sized: a total past `cap` writes nothing and is redone)
+    // no memset of the control block: the count pass zeroes the scan's status words,
+    // spills are counted in the handle's counter, which the scan moves into
+    // scalars[5] and re-arms
+    const unsigned grid = (unsigned)grid_for(p.A.rows, RowSmall::WPB);
+    // the numeric launch's scan words: ticket + tile status, then the group prefixes
+    unsigned long long* status = rowptr_scan_status(p);
+    const int64_t nscan = scan_tiles(p.A.rows);
+    const int64_t nstatus = nscan + 1 + row_groups(p.A.rows);
+    RowExt<IP>* ext = (RowExt<IP>*)p.ext;
+    RowScan<OUT> sa{nscan, (OUT*)cp, status, status + nscan + 1, p.scalars, nullptr, nullptr, nullptr, 0, 0,
+                    h->lb_spin};
+    if (!p.counts_ready) {
+        if (h->spill_ctr_dirty) SPG_HIP(h, hipMemsetAsync(h->spill_ctr, 0, sizeof(int32_t), h->stream));
+        h->spill_ctr_dirty = true;
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_row<double, IP, int64_t, ROW_SYM, RowSmall>, dim3(grid), dim3(RowSmall::WPB * WAVE),
+                           (int64_t)0, p.A.rows, p.B.cols, (const IP*)p.A.indptr,
+                           (const int32_t*)p.A.indices, (const double*)nullptr, (const IP*)p.B.indptr,
+                           (const int32_t*)p.B.indices, (const double*)nullptr, (const int64_t*)nullptr,
+                           (int32_t*)nullptr, (double*)nullptr, 1.0, p.row_cnt, p.spill, h->spill_ctr,
+                           (int)ROW_COUNT_ALL, (int64_t)0, (const int64_t*)nullptr, status, nstatus,
+                           ext, RowScan<int64_t>{});
         SPG_LAUNCHED(h);
-        return SPG_STATUS_SUCCESS;
+        // the scan blocks hand the spill count over (to scalars[5]), re-arm the counter and
+        // mirror total / overflow / spills into the pinned buffer
+        sa.move_cnt = h->spill_ctr;
+        sa.move_dst = p.scalars + 5;
+        sa.host_mirror = h->pinned;
+        sa.mirror_gen = ++h->mirror_gen;
+        sa.mirror_n = 2;   // words 0, 1 (+ 5: the move)
+        h->spill_ctr_dirty = false;
+    } else {   // repeated call: the first call already moved the spill count
+        SPG_HIP(h, hipMemsetAsync(status, 0, sizeof(unsigned long long) * (size_t)nstatus, h->stream));
     }
+    KernelTimer kt(h, SPG_PHASE_NUMERIC);
+    hipExtLaunchKernelGGL((k_row<T, IP, OUT, ROW_LB, RowSmall>), dim3((unsigned)(nscan + grid)),
+                          dim3(RowSmall::WPB * WAVE), 0, h->stream, kt.a, kt.b, 0, (int64_t)0, p.A.rows, p.B.cols,
+                          (const IP*)p.A.indptr, (const int32_t*)p.A.indices, (const T*)p.A.values,
+                          (const IP*)p.B.indptr, (const int32_t*)p.B.indices, (const T*)p.B.values,
+                          (const OUT*)nullptr, p.tj, (T*)p.tx, (T)1, p.row_cnt, p.spill, spill_counts(p, true),
+                          (int)ROW_LISTED, std::max<int64_t>(p.cap, 1), (const int64_t*)nullptr,
+                          (unsigned long long*)nullptr, (int64_t)0, ext, sa);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// ALG1 single pass on k_short: one launch writes C compact into tj/tx and its row pointer
+template <typename T, typename IP, typename OUT>
+spg_status_t alg1_short_launch(spg_handle_t h, spg_plan_s& p, void* cp) {
     PhaseTimer pt(h, SPG_PHASE_NUMERIC);
     hipLaunchKernelGGL((k_short<T, IP, OUT, SHORT_NUMLB, ShortSmall>), dim3((unsigned)grid_for(p.A.rows, ShortSmall::WPB)),
                        dim3(ShortSmall::WPB * WAVE), 0, h->stream, (int64_t)0, p.A.rows, p.B.cols,
@@ -1241,11 +1285,7 @@ spg_status_t alg1_fused_spills(spg_handle_t h, spg_plan_s& p, const void* cp) {
     return SPG_STATUS_SUCCESS;
 }
 
-template <typename T, typename IP>
-spg_status_t alg1_fused_typed(spg_handle_t h, spg_plan_s& p, void* cp, spg_index_t ct) {
-    return ct == SPG_INDEX_64I ? alg1_fused_run<T, IP, int64_t>(h, p, cp) : alg1_fused_run<T, IP, int32_t>(h, p, cp);
-}
-
+// The count pass of the two-phase row path: every row's entries of C into row_cnt, chunk by chunk
 template <typename IP>
 spg_status_t symbolic_typed(spg_handle_t h, spg_plan_s& p) {
     spg_status_t st;
@@ -1259,13 +1299,6 @@ spg_status_t symbolic_typed(spg_handle_t h, spg_plan_s& p) {
         return SPG_STATUS_SUCCESS;
     }
     return run_symbolic_rows<IP>(h, p, 0, p.A.rows, 0);
-}
-
-template <typename T, typename IP>
-spg_status_t alg1_compute(spg_handle_t h, spg_plan_s& p) {
-    // the fused structure+value pass at upper-bound offsets (the product prefix in p.ub,
-    // computed when the plan was built)
-    return run_numeric_rows<T, IP, int64_t, true>(h, p, 0, p.A.rows, 0, p.ub, p.tj, (T*)p.tx, (T)1);
 }
 
 template <typename T, typename IP, typename IPC>
@@ -1287,7 +1320,7 @@ spg_status_t numeric_typed(spg_handle_t h, spg_plan_s& p, const spg_csr_t& C, T 
         }
         return SPG_STATUS_SUCCESS;
     }
-    if (p.alg == SPG_ALG1 && !p.use_tile && !fused_alg1(p)) {
+    if (alg1_upper_bound(p)) {
         if (p.A.rows > 0) {
             PhaseTimer pt(h, SPG_PHASE_COMPACT);
             hipLaunchKernelGGL((k_compact<T, IPC>), dim3((unsigned)grid_for(p.A.rows, WPB)), dim3(BLOCK), 0,
@@ -1314,71 +1347,176 @@ spg_status_t numeric_typed(spg_handle_t h, spg_plan_s& p, const spg_csr_t& C, T 
                                                (T*)C.values, alpha);
 }
 
-template <typename IP>
-spg_status_t validate_typed(spg_handle_t h, const spg_csr_t& M, int* flags) {
-    if (M.rows > 0) {
-        PhaseTimer pt(h, SPG_PHASE_VALIDATE);
-        hipLaunchKernelGGL(k_validate<IP>, dim3((unsigned)grid_for(M.rows, BLOCK)), dim3(BLOCK), 0,
-                           h->stream, M.rows, M.cols, M.nnz, (const IP*)M.indptr,
-                           (const int32_t*)M.indices, flags);
-        SPG_LAUNCHED(h);
-    }
+// ------------------------------------------------------------------- spg_symbolic's paths
+// spg_symbolic takes one of four paths, chosen from the plan's shape (fused_alg1, use_row,
+// use_tile) and from fused_failed: ALG1's single pass on k_row, on k_short, the tiles, the rows.
+// A single pass that gives up sets fused_failed, and the rows path takes that call (k_short) or
+// the next one (k_row).  What a call leaves for the next spg_symbolic and for spg_numeric:
+//   counts_ready   row_cnt (tiles: the item offsets) is valid: a repeated call (the int64 retry
+//                  after SPG_STATUS_OVERFLOW) rescans it instead of counting again
+//   alg1_fused     C's indices and values stand compact in tj/tx (spg_result_in_workspace)
+//   fused_failed   the single pass met an output past `cap` or a row it refuses
+//   symbolic_runs  rows path: calls so far; from the second on the row-pointer scan's status
+//                  words are re-armed first (the plan zeroed them for the first)
+//   sym_spills     rows the short-row count pass listed; 0 lets spg_numeric skip its spill launch
+//   chunk_spills   the same per ALG3 chunk (nspc > 0: k_row counting its own spills)
+
+// A finished pass: what spg_numeric checks C against, and the caller's count
+spg_status_t symbolic_done(spg_plan_s& p, void* cp, spg_index_t ct, int64_t total, int64_t* nnzC) {
+    p.nnzC = total;
+    p.c_indptr = cp;
+    p.c_indptr_type = ct;
+    *nnzC = total;
     return SPG_STATUS_SUCCESS;
 }
 
-}  // namespace
+// the host's overflow rule of the k_short and tile paths (their last scan sets no device flag)
+inline bool past_int32(spg_index_t ct, int64_t total) { return ct == SPG_INDEX_32I && total > 2147483647LL; }
 
-// =============================================================================== C ABI
-// ---- 16-bit columns for the structure broadcast (include/spgemm.h, spg_cols16_*)
-// One wave per row.  Split: every column's low half, and where the row's columns reach each
-// interior block start c * 65536 (the first entry whose high half is >= c; the row length
-// when none is).  Each start is written by exactly one lane: the entry whose high half
-// steps over it, or the tail loop for blocks past the row's last column.
-template <typename IP>
-__global__ __launch_bounds__(256) void k_cols16_split(int64_t rows, const IP* __restrict__ Mp,
-                                                      const int32_t* __restrict__ Mj, int nb1,
-                                                      uint32_t* __restrict__ starts, uint16_t* __restrict__ lo16) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = lane_id();
-    const int64_t b = (int64_t)Mp[row];
-    const uint32_t len = (uint32_t)((int64_t)Mp[row + 1] - b);
-    uint32_t* __restrict__ st = starts + row * nb1;
-    for (uint32_t i = l; i < len; i += WAVE) {
-        const uint32_t c = (uint32_t)Mj[b + i];
-        lo16[b + i] = (uint16_t)(c & 0xffffu);
-        const int hi = min((int)(c >> 16), nb1);   // (clamped: a column past M's width writes nothing past the row's starts)
-        const int hp = i ? min((int)((uint32_t)Mj[b + i - 1] >> 16), nb1) : 0;
-        for (int q = hp + 1; q <= hi; ++q) st[q - 1] = i;
+// ALG1 on k_row: count pass (first call only), row-pointer scan, numeric pass into the
+// workspace's compact C -- no host sync in between.  A repeated call (the int64 retry after an
+// int32 overflow, when the numeric pass wrote nothing) redoes the scan and the numeric pass.
+spg_status_t symbolic_alg1_row(spg_handle_t h, spg_plan_s& p, void* cp, spg_index_t ct, int64_t* nnzC) {
+    spg_status_t st = dispatch_value(p.A.value_type, [&](auto tag) {
+        return dispatch_index(p.A.indptr_type, ct, [&](auto ip, auto out) {
+            return alg1_row_launch<decltype(tag), decltype(ip), decltype(out)>(h, p, cp);
+        });
+    });
+    if (st) return st;
+    int64_t sc[6];
+    if (!p.counts_ready) {
+        // the scan mirrored total / overflow / spills into the pinned buffer: wait for
+        // that (no device->host copy, no wait for the numeric pass)
+        if ((st = wait_mirror(h))) return st;
+        for (int i = 0; i < 6; ++i) sc[i] = ((volatile int64_t*)h->pinned)[i];
+    } else if ((st = read_scalars(h, p.scalars, 6, sc))) {
+        return st;
     }
-    const int hl = len ? (int)((uint32_t)Mj[b + len - 1] >> 16) : 0;
-    for (int q = hl + 1 + l; q <= nb1; q += WAVE) st[q - 1] = len;
+    p.counts_ready = true;
+    if (sc[1]) return SPG_STATUS_OVERFLOW;   // int32 row pointer: retry with int64
+    const uint32_t spills = (uint32_t)(sc[5] & 0xffffffffu);   // rows the count pass listed
+    if (sc[0] <= p.cap) {
+        p.alg1_fused = true;
+        if ((int32_t)spills > 0) {   // the listed rows' values, at Cp
+            st = dispatch_value(p.A.value_type, [&](auto tag) {
+                return dispatch_index(p.A.indptr_type, ct, [&](auto ip, auto out) {
+                    return alg1_fused_spills<decltype(tag), decltype(ip), decltype(out)>(h, p, cp);
+                });
+            });
+            if (st) return st;
+        }
+        return symbolic_done(p, cp, ct, sc[0], nnzC);
+    }
+    // an output larger than the estimate: spg_numeric redoes the numeric pass into C (the counts
+    // and the row pointer are valid), and a repeated spg_symbolic is the rows path's second call
+    p.fused_failed = true;
+    p.symbolic_runs = 1;
+    p.sym_spills = (int64_t)spills;   // the numeric pass relists them
+    SPG_HIP(h, hipMemsetAsync(p.scalars + 4, 0, 2 * sizeof(int64_t), h->stream));
+    return symbolic_done(p, cp, ct, sc[0], nnzC);
 }
 
-// Join: column = (block << 16) | low half, the block = the number of interior starts <= the
-// entry's offset in its row (the starts ascend; a binary search over the row's nb1 starts).
-template <typename IP>
-__global__ __launch_bounds__(256) void k_cols16_join(int64_t rows, const IP* __restrict__ Mp, int nb1,
-                                                     const uint32_t* __restrict__ starts,
-                                                     const uint16_t* __restrict__ lo16, int32_t* __restrict__ Mj) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = lane_id();
-    const int64_t b = (int64_t)Mp[row];
-    const uint32_t len = (uint32_t)((int64_t)Mp[row + 1] - b);
-    const uint32_t* __restrict__ st = starts + row * nb1;
-    for (uint32_t i = l; i < len; i += WAVE) {
-        int lo = 0, hi = nb1;   // first q with st[q] > i
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (st[mid] <= i) lo = mid + 1; else hi = mid;
-        }
-        Mj[b + i] = (int32_t)(((uint32_t)lo << 16) | (uint32_t)lo16[b + i]);
+spg_status_t symbolic_rows(spg_handle_t h, spg_plan_s& p, void* cp, spg_index_t ct, int64_t* nnzC);
+
+// ALG1 on k_short: one launch writes C compact into tj/tx and its row pointer; a repeated call
+// (int64 retry) only rescans the row counts it recorded.
+spg_status_t symbolic_alg1_short(spg_handle_t h, spg_plan_s& p, void* cp, spg_index_t ct, int64_t* nnzC) {
+    spg_status_t st;
+    ++p.symbolic_runs;
+    if (p.counts_ready) {   // (the pass held: alg1_fused is set)
+        SPG_HIP(h, hipMemsetAsync(rowptr_scan_status(p), 0, status_bytes(p.A.rows), h->stream));
+        if ((st = dispatch_index(ct, [&](auto out) { return run_scan<decltype(out)>(h, p, cp); }))) return st;
+        int64_t tot;   // the scan leaves the total in scalars[0]
+        if ((st = read_scalars(h, p.scalars, 1, &tot))) return st;
+        if (past_int32(ct, tot)) return SPG_STATUS_OVERFLOW;
+        return symbolic_done(p, cp, ct, tot, nnzC);
     }
+    st = dispatch_value(p.A.value_type, [&](auto tag) {
+        return dispatch_index(p.A.indptr_type, ct, [&](auto ip, auto out) {
+            return alg1_short_launch<decltype(tag), decltype(ip), decltype(out)>(h, p, cp);
+        });
+    });
+    if (st) return st;
+    int64_t sc[11];
+    if ((st = read_scalars(h, p.scalars, 11, sc))) return st;
+    if (sc[LB_FAIL] || sc[LB_CAPX]) {
+        // a row the single pass cannot take, or an output larger than the estimate: redo
+        // the product two-phase (symbolic + scan here, numeric straight into C)
+        p.fused_failed = true;
+        p.symbolic_runs = 0;
+        return symbolic_rows(h, p, cp, ct, nnzC);
+    }
+    // (both set before an int32 overflow returns: the int64 retry takes the rescan above)
+    p.counts_ready = true;
+    p.alg1_fused = true;
+    if (past_int32(ct, sc[LB_TOTAL])) return SPG_STATUS_OVERFLOW;
+    return symbolic_done(p, cp, ct, sc[LB_TOTAL], nnzC);
+}
+
+// The tile path: counts, offsets and row pointer chunk by chunk; the last scan leaves the total
+// in scalars[0].
+spg_status_t symbolic_tiles(spg_handle_t h, spg_plan_s& p, void* cp, spg_index_t ct, int64_t* nnzC) {
+    spg_status_t st = dispatch_index(p.A.indptr_type, ct, [&](auto ip, auto out) {
+        return tile_symbolic<decltype(ip), decltype(out)>(h, p, cp);
+    });
+    if (st) return st;
+    int64_t tot;
+    if ((st = read_scalars(h, p.scalars, 1, &tot))) return st;
+    p.counts_ready = true;
+    if (past_int32(ct, tot)) return SPG_STATUS_OVERFLOW;
+    return symbolic_done(p, cp, ct, tot, nnzC);
+}
+
+// The row kernels: ALG2, ALG3, ALG1 at upper-bound offsets, and ALG1's single pass after it
+// gave up.  Count pass (first call only), then the row-pointer scan.
+spg_status_t symbolic_rows(spg_handle_t h, spg_plan_s& p, void* cp, spg_index_t ct, int64_t* nnzC) {
+    spg_status_t st;
+    if (p.symbolic_runs++ > 0) {
+        // a repeated call (e.g. retrying with int64 row pointers): the row counts are kept;
+        // re-arm the row-pointer scan's status words
+        SPG_HIP(h, hipMemsetAsync(rowptr_scan_status(p), 0, status_bytes(p.A.rows), h->stream));
+    }
+    const bool counted = !p.counts_ready;   // this call runs the count pass
+    if (counted) {
+        if (alg1_upper_bound(p)) {
+            // the structure + value pass at upper-bound offsets (the product prefix in p.ub,
+            // computed when the plan was built)
+            st = dispatch_value(p.A.value_type, [&](auto tag) {
+                using T = decltype(tag);
+                return dispatch_index(p.A.indptr_type, [&](auto ip) {
+                    return run_numeric_rows<T, decltype(ip), int64_t, true>(h, p, 0, p.A.rows, 0, p.ub, p.tj,
+                                                                            (T*)p.tx, (T)1);
+                });
+            });
+        } else {
+            st = dispatch_index(p.A.indptr_type, [&](auto ip) { return symbolic_typed<decltype(ip)>(h, p); });
+        }
+        if (st) return st;
+    }
+    // the row-pointer scan mirrors the control words (+ every chunk's spill count) into the
+    // pinned buffer: no device->host copy
+    const bool chunks = p.nspc > 0 && counted;
+    const int nread = chunks ? 16 + p.nspc : 5;
+    if ((st = dispatch_index(ct, [&](auto out) { return run_scan<decltype(out)>(h, p, cp, nread); }))) return st;
+    std::vector<int64_t> all((size_t)nread);
+    if ((st = wait_mirror(h))) return st;
+    for (int i = 0; i < nread; ++i) all[(size_t)i] = ((volatile int64_t*)h->pinned)[i];
+    if (chunks) {
+        p.chunk_spills.assign(all.begin() + 16, all.end());
+        for (auto& v : p.chunk_spills) v &= 0xffffffffLL;
+    }
+    // the short-row kernel spills the same rows in both passes: none in the symbolic pass
+    // (one launch over all rows) means the numeric spill launch can be skipped.  Only a call that
+    // ran the count pass reads that count: on a repeated call the word may have been cleared for
+    // the numeric pass (ALG1's single pass that outgrew its estimate set sym_spills itself)
+    if (counted && p.use_short && (p.alg == SPG_ALG2 || fused_alg1(p)))
+        p.sym_spills = (int64_t)(uint32_t)(all[4] & 0xffffffffu);
+    p.counts_ready = true;      // counts stay valid for a repeated call
+    if (all[1]) return SPG_STATUS_OVERFLOW;   // (the scan's device flag)
+    return symbolic_done(p, cp, ct, all[0], nnzC);
 }
 
 // ----------------------------------------------------------------------------- SpMM
-namespace {
 
 spg_status_t check_dense(const spg_dense_t* D) {
     if (!D || D->rows < 0 || D->cols < 0) return SPG_STATUS_INVALID_VALUE;
@@ -1438,8 +1576,400 @@ spg_status_t spmm_launch(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& 
     return SPG_STATUS_SUCCESS;
 }
 
+// ----------------------------------------------------------------------------- spg_csr2csc
+
+// Workspace carve of spg_csr2csc (offsets from the 256-byte aligned base).
+struct TrLayout {
+    int passes = 1;            // 8-bit digit passes: the bytes of cols - 1 (at least one)
+    int64_t chunks = 0;        // wave chunks of TR_CHUNK entries
+    int nbuf = 0;              // ping-pong record buffers the passes need (0, 1 or 2)
+    size_t scalars = 0, status = 0, table = 0, skeys = 0, buf[2] = {0, 0};
+    size_t keys = 0, rowids = 0, pos = 0;   // inside one record buffer
+    size_t total = 0;          // bytes to ask for (256 of slack for the base alignment)
+};
+
+TrLayout tr_layout(const spg_csr_t& A) {
+    TrLayout L;
+    const size_t ips = index_bytes(A.indptr_type);
+    const uint64_t top = A.cols > 0 ? (uint64_t)(A.cols - 1) : 0;
+    L.passes = top >= (1ull << 24) ? 4 : top >= (1ull << 16) ? 3 : top >= (1ull << 8) ? 2 : 1;
+    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
+    L.nbuf = std::min(L.passes - 1, 2);
+    Carver c;
+    L.scalars = c.take(16 * sizeof(int64_t));
+    L.status = c.take(status_bytes(TR_RADIX * L.chunks));
+    L.table = c.take(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
+    L.skeys = c.take(sizeof(int32_t) * (size_t)A.nnz);   // the sorted columns (the last pass -> k_tr_indptr)
+    Carver rec;   // one record buffer: keys | row ids | positions
+    L.keys = rec.take(sizeof(int32_t) * (size_t)A.nnz);
+    L.rowids = rec.take(sizeof(int32_t) * (size_t)A.nnz);
+    L.pos = rec.take(ips * (size_t)A.nnz);
+    for (int b = 0; b < L.nbuf; ++b) L.buf[b] = c.take(rec.off);
+    L.total = c.off + 256;
+    return L;
+}
+
+template <typename IP>
+spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrLayout& L, char* ws) {
+    const int64_t nnz = A.nnz, chunks = L.chunks;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    unsigned long long* status = (unsigned long long*)(ws + L.status);
+    IP* table = (IP*)(ws + L.table);
+    IP* ATp = (IP*)AT.indptr;
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    const int32_t* kin = (const int32_t*)A.indices;
+    const int32_t* rin = nullptr;
+    const IP* pin = nullptr;
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = 8 * p;
+        const bool first = p == 0, last = p == L.passes - 1;
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP>, grid, block, nnz, chunks, TrKeys{kin}, shift, table);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
+        char* out = last ? nullptr : ws + L.buf[p & 1];
+        int32_t* kout = last ? (int32_t*)(ws + L.skeys) : (int32_t*)(out + L.keys);
+        int32_t* rout = last ? nullptr : (int32_t*)(out + L.rowids);
+        IP* pout = last ? nullptr : (IP*)(out + L.pos);
+        if (!last) {
+            using V = uint32_t;   // (no value is touched before the last pass)
+            if (first)
+                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, false>, grid, block, nnz, chunks, shift,
+                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
+                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
+            else
+                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, false>, grid, block, nnz, chunks, shift,
+                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
+                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
+        } else {
+            auto run_last = [&](auto vtag) {
+                using V = decltype(vtag);
+                if (first)
+                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, true>, grid, block, nnz, chunks,
+                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
+                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
+                else
+                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, true>, grid, block, nnz, chunks,
+                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
+                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
+            };
+            switch (vbytes(A.value_type)) {
+                case 4: run_last(TrBits<4>::type{}); break;
+                case 8: run_last(TrBits<8>::type{}); break;
+                default: run_last(TrBits<16>::type{}); break;
+            }
+        }
+        SPG_LAUNCHED(h);
+        kin = kout;
+        rin = rout;
+        pin = pout;
+    }
+    // (kin: the sorted columns the last pass left)
+    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
+    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP, IP>, dim3(pgrid), dim3(256), nnz, A.cols, TrKeys{kin}, ATp,
+                 (const IP*)nullptr);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// ----------------------------------------------------------------------------- spg_csrgeam
+
+// Workspace carve of spg_csrgeam_nnz / spg_csrgeam (offsets from the 256-byte aligned base).
+struct GmLayout {
+    int64_t chunksA = 0, chunksB = 0;   // wave chunks of GM_CHUNK entries
+    size_t scalars = 0;                 // 16 int64: [0] a scan's total, [1] its overflow flag
+    size_t status_b = 0, status_r = 0;  // look-back words of the scan over B's entries / over the rows
+    size_t S = 0;                       // nnz(B) + 1 IP: B-only marks, scanned in place (kept for the value pass)
+    size_t cnt = 0;                     // rows + 1 int64: entries per row of C
+    size_t total = 0;                   // bytes to ask for (256 of slack for the base alignment)
+};
+
+GmLayout gm_layout(const spg_csr_t& A, const spg_csr_t& B) {
+    GmLayout L;
+    const size_t ips = index_bytes(A.indptr_type);
+    L.chunksA = (A.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    L.chunksB = (B.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    Carver c;
+    L.scalars = c.take(16 * sizeof(int64_t));
+    L.status_b = c.take(status_bytes(B.nnz));
+    L.status_r = c.take(status_bytes(A.rows));
+    L.S = c.take(ips * ((size_t)B.nnz + 1));
+    L.cnt = c.take(sizeof(int64_t) * ((size_t)A.rows + 1));
+    L.total = c.off + 256;
+    return L;
+}
+
+// what both entry points ask of the operands
+spg_status_t gm_check(const spg_csr_t* A, const spg_csr_t* B) {
+    if (!A || !B) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = check_csr(A);
+    if (st || (st = check_csr(B))) return st;
+    if (A->rows != B->rows || A->cols != B->cols || A->value_type != B->value_type ||
+        A->indptr_type != B->indptr_type)
+        return SPG_STATUS_INVALID_VALUE;
+    return SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP>
+spg_status_t gm_structure(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, const GmLayout& L, char* ws,
+                          CP* Cp, int64_t* nnzC) {
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    IP* S = (IP*)(ws + L.S);
+    int64_t* cnt = (int64_t*)(ws + L.cnt);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if (B.nnz > 0) {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_mark<IP>, dim3((unsigned)grid_for(L.chunksB, GM_WPB)),
+                     dim3(GM_WPB * WAVE), A.rows, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices,
+                     (const IP*)B.indptr, (const int32_t*)B.indices, S);
+        SPG_LAUNCHED(h);
+    }
+    if ((st = launch_scan<IP, IP>(h, B.nnz, S, S, (unsigned long long*)(ws + L.status_b), scal, true))) return st;
+    const unsigned cgrid = (unsigned)std::min<int64_t>(grid_for(A.rows, 256), 1 << 20);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_count<IP>, dim3(cgrid), dim3(256), A.rows, (const IP*)A.indptr,
+                 (const IP*)B.indptr, (const IP*)S, cnt);
+    SPG_LAUNCHED(h);
+    if ((st = launch_scan<CP, int64_t>(h, A.rows, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
+        return st;
+    int64_t sc[2] = {0, 0};
+    if ((st = read_scalars(h, scal, 2, sc))) return st;
+    *nnzC = sc[0];
+    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP, typename T>
+spg_status_t gm_values(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, spg_csr_t& C, const GmLayout& L,
+                       char* ws, T alpha, T beta) {
+    timed_launch(h, SPG_PHASE_NUMERIC, k_geam_fill<IP, CP, T>,
+                 dim3((unsigned)grid_for(L.chunksA + L.chunksB, GM_WPB)), dim3(GM_WPB * WAVE), A.rows, A.nnz,
+                 L.chunksA, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices, (const T*)A.values,
+                 (const IP*)B.indptr, (const int32_t*)B.indices, (const T*)B.values, (const IP*)(ws + L.S),
+                 (const CP*)C.indptr, (int32_t*)C.indices, (T*)C.values, alpha, beta);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// ----------------------------------------------------------------------------- spg_canonicalize
+
+// bits of an index below `extent`: the bits of extent - 1 (at least one)
+inline int index_bits(int64_t extent) {
+    int b = 1;
+    while (b < 63 && ((int64_t)1 << b) < extent) ++b;
+    return b;
+}
+
+// Workspace carve of spg_canonicalize_nnz / spg_canonicalize (offsets from the 256-byte aligned
+// base).  The sorted records stay in buf[passes & 1] and the scanned marks in `kept` for the
+// value call.
+struct CnLayout {
+    bool sum = false, drop = false;
+    bool marks = false;         // SUM or DROP_ZEROS: kept[] exists
+    int cbits = 1, rbits = 1;   // key = row << cbits | column
+    bool k64 = false;           // the key takes 64 bits
+    int shift0 = 0;             // the first digit's shift: 0, or cbits when only the rows are sorted (COO, no op)
+    int passes = 0;             // 0: CSR input with DROP_ZEROS alone, no sort (the entries are their own records)
+    int64_t chunks = 0;         // wave chunks of TR_CHUNK entries
+    size_t scalars = 0;         // 16 int64: [0] a scan's total
+    size_t status_t = 0, status_k = 0;   // look-back words of the table scans / of the scan over kept[]
+    size_t table = 0;           // 256 * chunks + 1 IP: a pass's digit histogram, scanned in place
+    size_t kept = 0;            // nnz + 1 IP: the kept marks, scanned in place
+    size_t buf[2] = {0, 0};     // ping-pong record buffers (k_cn_pack writes buf[0])
+    size_t total = 0;           // bytes to ask for (256 of slack for the base alignment)
+};
+
+CnLayout cn_layout(const spg_csr_t& A, bool coo, unsigned ops) {
+    CnLayout L;
+    const size_t ips = index_bytes(A.indptr_type);
+    const size_t nnz = (size_t)A.nnz;
+    L.sum = (ops & SPG_CANON_SUM) != 0;
+    L.drop = (ops & SPG_CANON_DROP_ZEROS) != 0;
+    L.marks = L.sum || L.drop;
+    const bool sort = L.sum || (ops & SPG_CANON_SORT) != 0;
+    L.cbits = index_bits(A.cols);
+    L.rbits = index_bits(A.rows);
+    L.k64 = L.cbits + L.rbits > 32;
+    L.shift0 = sort ? 0 : L.cbits;
+    L.passes = sort || coo ? (L.cbits + L.rbits - L.shift0 + 7) / 8 : 0;
+    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
+    Carver c;
+    L.scalars = c.take(16 * sizeof(int64_t));
+    if (L.passes) {
+        L.status_t = c.take(status_bytes(TR_RADIX * L.chunks));
+        L.table = c.take(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
+    }
+    if (L.marks) {
+        L.status_k = c.take(status_bytes(A.nnz));
+        L.kept = c.take(ips * (nnz + 1));
+    }
+    const size_t rec = (ips == 4 && !L.k64 ? 8 : 16) * nnz;   // sizeof(CnRec<IP, K>) each
+    for (int b = 0; b < (L.passes ? 2 : 0); ++b) L.buf[b] = c.take(rec);
+    L.total = c.off + 256;
+    return L;
+}
+
+// what both entry points ask of the input
+spg_status_t cn_check(const spg_csr_t* A, const int32_t* coo_rows, unsigned ops) {
+    if (!A) return SPG_STATUS_INVALID_VALUE;
+    if (A->rows < 0 || A->cols < 0 || A->nnz < 0) return SPG_STATUS_INVALID_VALUE;
+    if (A->cols > 2147483647LL || A->rows > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;   // int32 ids
+    if (A->indptr_type != SPG_INDEX_32I && A->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    if (A->value_type != SPG_R_32F && A->value_type != SPG_R_64F && A->value_type != SPG_C_32F &&
+        A->value_type != SPG_C_64F)
+        return SPG_STATUS_NOT_SUPPORTED;
+    if (A->indptr_type == SPG_INDEX_32I && A->nnz > 2147483647LL) return SPG_STATUS_INVALID_VALUE;
+    if (ops & ~(unsigned)(SPG_CANON_SORT | SPG_CANON_SUM | SPG_CANON_DROP_ZEROS)) return SPG_STATUS_INVALID_VALUE;
+    if (!coo_rows && (!A->indptr || ops == 0)) return SPG_STATUS_INVALID_VALUE;   // CSR: something to do
+    if (A->nnz > 0 && (!A->indices || !A->values)) return SPG_STATUS_INVALID_VALUE;
+    if (A->nnz > 0 && (A->rows == 0 || A->cols == 0)) return SPG_STATUS_INVALID_VALUE;
+    return SPG_STATUS_SUCCESS;
+}
+
+// the sorted records the structure call left (nullptr: unsorted, A's entries themselves)
+template <typename IP, typename K>
+const CnRec<IP, K>* cn_records(const CnLayout& L, char* ws) {
+    return L.passes ? (const CnRec<IP, K>*)(ws + L.buf[L.passes & 1]) : nullptr;
+}
+
+template <typename IP, typename K>
+spg_status_t cn_sort(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows, const CnLayout& L, char* ws) {
+    using Rec = CnRec<IP, K>;
+    static_assert(sizeof(Rec) == (sizeof(IP) + sizeof(K) == 8 ? 8 : 16), "cn_layout's record size");
+    const int64_t nnz = A.nnz, chunks = L.chunks;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    unsigned long long* status = (unsigned long long*)(ws + L.status_t);
+    IP* table = (IP*)(ws + L.table);
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    auto pack = coo_rows ? k_cn_pack<IP, K, CN_FROM_COO> : k_cn_pack<IP, K, CN_FROM_CSR>;
+    timed_launch(h, SPG_PHASE_LAYOUT, pack, grid, block, nnz, chunks, L.cbits, (const int32_t*)A.indices, coo_rows,
+                 (const IP*)A.indptr, A.rows, (Rec*)(ws + L.buf[0]));
+    SPG_LAUNCHED(h);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = L.shift0 + 8 * p;
+        const Rec* in = (const Rec*)(ws + L.buf[p & 1]);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP, CnKeys<IP, K>>, grid, block, nnz, chunks,
+                     CnKeys<IP, K>{in, 0}, shift, table);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
+        timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<IP, K>, grid, block, nnz, chunks, shift, in,
+                     (const IP*)table, (Rec*)(ws + L.buf[(p + 1) & 1]));
+        SPG_LAUNCHED(h);
+    }
+    return SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP, typename K>
+spg_status_t cn_structure(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows, const CnLayout& L, char* ws,
+                          CP* Cp, int64_t* nnzC) {
+    const int64_t nnz = A.nnz;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if (L.passes && (st = cn_sort<IP, K>(h, A, coo_rows, L, ws))) return st;
+    const CnRec<IP, K>* rec = cn_records<IP, K>(L, ws);
+    IP* kept = L.marks ? (IP*)(ws + L.kept) : nullptr;
+    if (L.marks) {
+        const dim3 grid((unsigned)grid_for(nnz, CN_BLOCK)), block(CN_BLOCK);
+        if (!L.drop) {   // (no value is read)
+            timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_mark<IP, K, uint32_t, true, false>, grid, block, nnz, rec,
+                         (const uint32_t*)nullptr, kept);
+        } else {
+            st = dispatch_value(A.value_type, [&](auto tag) {
+                using T = decltype(tag);
+                auto mark = L.sum ? k_cn_mark<IP, K, T, true, true> : k_cn_mark<IP, K, T, false, true>;
+                timed_launch(h, SPG_PHASE_SYMBOLIC, mark, grid, block, nnz, rec, (const T*)A.values, kept);
+                return SPG_STATUS_SUCCESS;
+            });
+            if (st) return st;
+        }
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<IP, IP>(h, nnz, kept, kept, (unsigned long long*)(ws + L.status_k), scal, true)))
+            return st;
+    }
+    if (L.passes) {   // off the sorted keys' rows
+        const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.rows + 1, 256), 1 << 20);
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_tr_indptr<IP, CP, CnKeys<IP, K>>, dim3(pgrid), dim3(256), nnz, A.rows,
+                     CnKeys<IP, K>{rec, L.cbits}, Cp, (const IP*)kept);
+    } else {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_indptr<IP, CP>, dim3((unsigned)grid_for(A.rows + 1, CN_BLOCK)),
+                     dim3(CN_BLOCK), A.rows, (const IP*)A.indptr, (const IP*)kept, Cp);
+    }
+    SPG_LAUNCHED(h);
+    *nnzC = nnz;
+    if (L.marks) {
+        int64_t total = 0;
+        if ((st = read_scalars(h, scal, 1, &total))) return st;
+        *nnzC = total;
+    }
+    return (sizeof(CP) == 4 && *nnzC > 2147483647LL) ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename K, typename T, bool SUM>
+spg_status_t cn_values(spg_handle_t h, const spg_csr_t& A, spg_csr_t& C, const CnLayout& L, char* ws) {
+    const K cmask = (K)(((uint64_t)1 << L.cbits) - 1);
+    timed_launch(h, SPG_PHASE_NUMERIC, k_cn_fill<IP, K, T, SUM>, dim3((unsigned)grid_for(A.nnz, CN_BLOCK)),
+                 dim3(CN_BLOCK), A.nnz, cn_records<IP, K>(L, ws), cmask, (const int32_t*)A.indices,
+                 (const T*)A.values, L.marks ? (const IP*)(ws + L.kept) : (const IP*)nullptr, (int32_t*)C.indices,
+                 (T*)C.values);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// f(IP{}, K{}) with the position and key types of this input
+template <typename F>
+spg_status_t cn_dispatch(const spg_csr_t& A, const CnLayout& L, F&& f) {
+    return dispatch_index(A.indptr_type, [&](auto ip) { return L.k64 ? f(ip, uint64_t(0)) : f(ip, uint32_t(0)); });
+}
+
 }  // namespace
 
+// ---- 16-bit columns for the structure broadcast (include/spgemm.h, spg_cols16_*)
+// One wave per row.  Split: every column's low half, and where the row's columns reach each
+// interior block start c * 65536 (the first entry whose high half is >= c; the row length
+// when none is).  Each start is written by exactly one lane: the entry whose high half
+// steps over it, or the tail loop for blocks past the row's last column.
+template <typename IP>
+__global__ __launch_bounds__(256) void k_cols16_split(int64_t rows, const IP* __restrict__ Mp,
+                                                      const int32_t* __restrict__ Mj, int nb1,
+                                                      uint32_t* __restrict__ starts, uint16_t* __restrict__ lo16) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int l = lane_id();
+    const int64_t b = (int64_t)Mp[row];
+    const uint32_t len = (uint32_t)((int64_t)Mp[row + 1] - b);
+    uint32_t* __restrict__ st = starts + row * nb1;
+    for (uint32_t i = l; i < len; i += WAVE) {
+        const uint32_t c = (uint32_t)Mj[b + i];
+        lo16[b + i] = (uint16_t)(c & 0xffffu);
+        const int hi = min((int)(c >> 16), nb1);   // (clamped: a column past M's width writes nothing past the row's starts)
+        const int hp = i ? min((int)((uint32_t)Mj[b + i - 1] >> 16), nb1) : 0;
+        for (int q = hp + 1; q <= hi; ++q) st[q - 1] = i;
+    }
+    const int hl = len ? (int)((uint32_t)Mj[b + len - 1] >> 16) : 0;
+    for (int q = hl + 1 + l; q <= nb1; q += WAVE) st[q - 1] = len;
+}
+
+// Join: column = (block << 16) | low half, the block = the number of interior starts <= the
+// entry's offset in its row (the starts ascend; a binary search over the row's nb1 starts).
+template <typename IP>
+__global__ __launch_bounds__(256) void k_cols16_join(int64_t rows, const IP* __restrict__ Mp, int nb1,
+                                                     const uint32_t* __restrict__ starts,
+                                                     const uint16_t* __restrict__ lo16, int32_t* __restrict__ Mj) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int l = lane_id();
+    const int64_t b = (int64_t)Mp[row];
+    const uint32_t len = (uint32_t)((int64_t)Mp[row + 1] - b);
+    const uint32_t* __restrict__ st = starts + row * nb1;
+    for (uint32_t i = l; i < len; i += WAVE) {
+        int lo = 0, hi = nb1;   // first q with st[q] > i
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (st[mid] <= i) lo = mid + 1; else hi = mid;
+        }
+        Mj[b + i] = (int32_t)(((uint32_t)lo << 16) | (uint32_t)lo16[b + i]);
+    }
+}
+
+// =============================================================================== C ABI
 extern "C" {
 
 int spg_version(void) { return SPG_VERSION_MAJOR * 10000 + SPG_VERSION_MINOR * 100 + SPG_VERSION_PATCH; }
@@ -1584,7 +2114,7 @@ spg_status_t spg_plan(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, sp
         const double est = 1.15 * (double)A->nnz * avgB + 4096.0;
         const double full = (double)A->rows * (double)B->cols;
         tmp.cap = (int64_t)std::min(est, full);
-    } else if (tmp.alg == SPG_ALG1 && !tmp.use_tile) {
+    } else if (alg1_upper_bound(tmp)) {
         if (workspace && same_as_query) {
             tmp.P = h->q_P;
         } else if ((st = products_total(h, *A, *B, &tmp.P))) {
@@ -1640,11 +2170,7 @@ spg_status_t spg_plan(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, sp
         h->q_seg_len = tmp.seg_len;
     }
     const Layout L = make_layout(tmp);
-    if (!workspace) {
-        *workspace_bytes = L.total;
-        return SPG_STATUS_SUCCESS;
-    }
-    if (*workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;
     spg_plan_s* p = new (std::nothrow) spg_plan_s(std::move(tmp));
     if (!p) return SPG_STATUS_ALLOC_FAILED;
     p->ws = (char*)workspace;
@@ -1657,7 +2183,7 @@ spg_status_t spg_plan(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, sp
                                                      : hipMemsetAsync(p->ws, 0, L.row_cnt, h->stream);
         if (e1 != hipSuccess) { delete p; return hip_fail(h, e1); }
     }
-    if (p->alg == SPG_ALG1 && !p->use_tile && !fused_alg1(*p)) {
+    if (alg1_upper_bound(*p)) {
         // upper-bound offsets for the single pass: product prefix straight into the workspace
         spg_status_t st2 = products_prefix(h, p->A, p->B, p->row_cnt, p->ub, p->scalars + 2,
                                            p->scan_status, false);
@@ -1687,183 +2213,12 @@ spg_status_t spg_symbolic(spg_handle_t h, spg_plan_t p, void* C_indptr, spg_inde
     if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    spg_status_t st;
-    const bool i64 = p->A.indptr_type == SPG_INDEX_64I;
-    if (fused_alg1(*p) && !p->fused_failed && p->use_row) {
-        // ALG1 on k_row: count pass (first call only), row-pointer scan, numeric pass into
-        // the workspace's compact C -- no host sync in between.  A repeated call (the int64
-        // retry after an int32 overflow, when the numeric pass wrote nothing) redoes the
-        // scan and the numeric pass.
-        st = dispatch_value(p->A.value_type, [&](auto tag) {
-            using T = decltype(tag);
-            return i64 ? alg1_fused_typed<T, int64_t>(h, *p, C_indptr, C_indptr_type)
-                       : alg1_fused_typed<T, int32_t>(h, *p, C_indptr, C_indptr_type);
-        });
-        if (st) return st;
-        int64_t sc[6];
-        if (!p->counts_ready) {
-            // the scan mirrored total / overflow / spills into the pinned buffer: wait for
-            // that (no device->host copy, no wait for the numeric pass)
-            if ((st = wait_mirror(h))) return st;
-            for (int i = 0; i < 6; ++i) sc[i] = ((volatile int64_t*)h->pinned)[i];
-        } else if ((st = read_scalars(h, p->scalars, 6, sc))) {
-            return st;
-        }
-        p->counts_ready = true;
-        if (sc[1]) return SPG_STATUS_OVERFLOW;   // int32 row pointer: retry with int64
-        if (sc[0] <= p->cap) {
-            p->alg1_fused = true;
-            if ((int32_t)(sc[5] & 0xffffffffu) > 0) {   // the listed rows' values, at Cp
-                st = dispatch_value(p->A.value_type, [&](auto tag) {
-                    using T = decltype(tag);
-                    if (i64)
-                        return C_indptr_type == SPG_INDEX_64I ? alg1_fused_spills<T, int64_t, int64_t>(h, *p, C_indptr)
-                                                              : alg1_fused_spills<T, int64_t, int32_t>(h, *p, C_indptr);
-                    return C_indptr_type == SPG_INDEX_64I ? alg1_fused_spills<T, int32_t, int64_t>(h, *p, C_indptr)
-                                                          : alg1_fused_spills<T, int32_t, int32_t>(h, *p, C_indptr);
-                });
-                if (st) return st;
-            }
-            p->nnzC = sc[0];
-            p->c_indptr = C_indptr;
-            p->c_indptr_type = C_indptr_type;
-            *nnzC = sc[0];
-            return SPG_STATUS_SUCCESS;
-        }
-        // an output larger than the estimate: redo the numeric pass into C (the counts and
-        // the row pointer are valid)
-        p->fused_failed = true;
-        p->symbolic_runs = 1;
-        p->sym_spills = (int64_t)(uint32_t)(sc[5] & 0xffffffffu);   // the numeric pass relists them
-        SPG_HIP(h, hipMemsetAsync(p->scalars + 4, 0, 2 * sizeof(int64_t), h->stream));
-        p->nnzC = sc[0];
-        p->c_indptr = C_indptr;
-        p->c_indptr_type = C_indptr_type;
-        *nnzC = sc[0];
-        return SPG_STATUS_SUCCESS;
-    }
-    if (fused_alg1(*p) && !p->fused_failed) {
-        // ALG1 single pass: one launch writes C compact into tj/tx and its row pointer; a
-        // repeated call (int64 retry) only rescans the row counts it recorded
-        ++p->symbolic_runs;
-        if (!p->counts_ready) {
-            st = dispatch_value(p->A.value_type, [&](auto tag) {
-                using T = decltype(tag);
-                return i64 ? alg1_fused_typed<T, int64_t>(h, *p, C_indptr, C_indptr_type)
-                           : alg1_fused_typed<T, int32_t>(h, *p, C_indptr, C_indptr_type);
-            });
-        } else {
-            const int64_t tiles = scan_tiles(p->A.rows) + 1;
-            SPG_HIP(h, hipMemsetAsync(p->scan_status + tiles, 0, sizeof(unsigned long long) * tiles, h->stream));
-            st = C_indptr_type == SPG_INDEX_64I ? run_scan<int64_t>(h, *p, C_indptr)
-                                                : run_scan<int32_t>(h, *p, C_indptr);
-            if (!st) {   // the scan leaves the total in scalars[0]
-                int64_t tot;
-                if ((st = read_scalars(h, p->scalars, 1, &tot))) return st;
-                if (C_indptr_type == SPG_INDEX_32I && tot > 2147483647LL) return SPG_STATUS_OVERFLOW;
-                p->nnzC = tot;
-                p->c_indptr = C_indptr;
-                p->c_indptr_type = C_indptr_type;
-                *nnzC = tot;
-                return SPG_STATUS_SUCCESS;
-            }
-        }
-        if (st) return st;
-        int64_t sc[11];
-        if ((st = read_scalars(h, p->scalars, 11, sc))) return st;
-        if (!sc[LB_FAIL] && !sc[LB_CAPX]) {
-            p->counts_ready = true;
-            p->alg1_fused = true;
-            const int64_t tot = sc[LB_TOTAL];
-            if (C_indptr_type == SPG_INDEX_32I && tot > 2147483647LL) return SPG_STATUS_OVERFLOW;
-            // k_row spilled rows (counted, row pointer written): their values, at that offset
-            if (p->use_row && (int32_t)(sc[5] & 0xffffffffu) > 0) {
-                st = dispatch_value(p->A.value_type, [&](auto tag) {
-                    using T = decltype(tag);
-                    if (i64)
-                        return C_indptr_type == SPG_INDEX_64I ? alg1_fused_spills<T, int64_t, int64_t>(h, *p, C_indptr)
-                                                              : alg1_fused_spills<T, int64_t, int32_t>(h, *p, C_indptr);
-                    return C_indptr_type == SPG_INDEX_64I ? alg1_fused_spills<T, int32_t, int64_t>(h, *p, C_indptr)
-                                                          : alg1_fused_spills<T, int32_t, int32_t>(h, *p, C_indptr);
-                });
-                if (st) return st;
-            }
-            p->nnzC = tot;
-            p->c_indptr = C_indptr;
-            p->c_indptr_type = C_indptr_type;
-            *nnzC = tot;
-            return SPG_STATUS_SUCCESS;
-        }
-        // a row the single pass cannot take, or an output larger than the estimate: redo
-        // the product two-phase (symbolic + scan here, numeric straight into C)
-        p->fused_failed = true;
-        p->symbolic_runs = 0;
-    }
-    if (p->use_tile) {
-        // counts, offsets and row pointer chunk by chunk; the last scan leaves the total in
-        // scalars[0] (overflow of an int32 row pointer is checked here)
-        st = i64 ? (C_indptr_type == SPG_INDEX_64I ? tile_symbolic<int64_t, int64_t>(h, *p, C_indptr)
-                                                   : tile_symbolic<int64_t, int32_t>(h, *p, C_indptr))
-                 : (C_indptr_type == SPG_INDEX_64I ? tile_symbolic<int32_t, int64_t>(h, *p, C_indptr)
-                                                   : tile_symbolic<int32_t, int32_t>(h, *p, C_indptr));
-        if (st) return st;
-        int64_t tot;
-        if ((st = read_scalars(h, p->scalars, 1, &tot))) return st;
-        p->counts_ready = true;
-        if (C_indptr_type == SPG_INDEX_32I && tot > 2147483647LL) return SPG_STATUS_OVERFLOW;
-        p->nnzC = tot;
-        p->c_indptr = C_indptr;
-        p->c_indptr_type = C_indptr_type;
-        *nnzC = tot;
-        return SPG_STATUS_SUCCESS;
-    }
-    if (p->symbolic_runs++ > 0 && !p->use_tile) {
-        // a repeated call (e.g. retrying with int64 row pointers): the row counts are kept;
-        // re-arm the row-pointer scan's status words
-        const int64_t tiles = scan_tiles(p->A.rows) + 1;
-        SPG_HIP(h, hipMemsetAsync(p->scan_status + tiles, 0, sizeof(unsigned long long) * tiles, h->stream));
-    }
-    if (!p->counts_ready) {
-        if (p->alg == SPG_ALG1 && !p->use_tile && !fused_alg1(*p)) {
-            st = dispatch_value(p->A.value_type, [&](auto tag) {
-                using T = decltype(tag);
-                return i64 ? alg1_compute<T, int64_t>(h, *p) : alg1_compute<T, int32_t>(h, *p);
-            });
-        } else {
-            st = i64 ? symbolic_typed<int64_t>(h, *p) : symbolic_typed<int32_t>(h, *p);
-        }
-        if (st) return st;
-    }
-    // the row-pointer scan mirrors the control words (+ every chunk's spill count) into the
-    // pinned buffer: no device->host copy
-    const bool counted = !p->counts_ready;   // this call ran the count pass
-    const bool chunks = p->nspc > 0 && counted;
-    const int nread = chunks ? 16 + p->nspc : 5;
-    st = C_indptr_type == SPG_INDEX_64I ? run_scan<int64_t>(h, *p, C_indptr, nread)
-                                        : run_scan<int32_t>(h, *p, C_indptr, nread);
-    if (st) return st;
-    std::vector<int64_t> all((size_t)nread);
-    if ((st = wait_mirror(h))) return st;
-    for (int i = 0; i < nread; ++i) all[(size_t)i] = ((volatile int64_t*)h->pinned)[i];
-    int64_t sc[5];
-    for (int i = 0; i < 5; ++i) sc[i] = all[(size_t)i];
-    if (chunks) {
-        p->chunk_spills.assign(all.begin() + 16, all.end());
-        for (auto& v : p->chunk_spills) v &= 0xffffffffLL;
-    }
-    // the short-row kernel spills the same rows in both passes: none in the symbolic pass
-    // (one launch over all rows) means the numeric spill launch can be skipped.  Only a call that
-    // ran the count pass reads that count: on a repeated call the word may have been cleared for
-    // the numeric pass (ALG1's single pass that outgrew its estimate set sym_spills itself)
-    if (counted && p->use_short && (p->alg == SPG_ALG2 || fused_alg1(*p)))
-        p->sym_spills = (int64_t)(uint32_t)(sc[4] & 0xffffffffu);
-    p->counts_ready = true;      // counts stay valid for a repeated call
-    if (sc[1]) return SPG_STATUS_OVERFLOW;
-    p->nnzC = sc[0];
-    p->c_indptr = C_indptr;
-    p->c_indptr_type = C_indptr_type;
-    *nnzC = sc[0];
-    return SPG_STATUS_SUCCESS;
+    // ALG1's single pass until it has given up; then, as for every other plan, the tiles or the rows
+    if (fused_alg1(*p) && !p->fused_failed)
+        return p->use_row ? symbolic_alg1_row(h, *p, C_indptr, C_indptr_type, nnzC)
+                          : symbolic_alg1_short(h, *p, C_indptr, C_indptr_type, nnzC);
+    if (p->use_tile) return symbolic_tiles(h, *p, C_indptr, C_indptr_type, nnzC);
+    return symbolic_rows(h, *p, C_indptr, C_indptr_type, nnzC);
 }
 
 spg_status_t spg_numeric(spg_handle_t h, spg_plan_t p, const void* alpha, spg_csr_t* C) {
@@ -1878,16 +2233,13 @@ spg_status_t spg_numeric(spg_handle_t h, spg_plan_t p, const void* alpha, spg_cs
     if (p->nnzC == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    const bool i64 = p->A.indptr_type == SPG_INDEX_64I;
-    const bool c64 = C->indptr_type == SPG_INDEX_64I;
     return dispatch_value(p->A.value_type, [&](auto tag) {
         using T = decltype(tag);
         T a;
         std::memcpy(&a, alpha, sizeof(T));   // host value of C's type (a (re, im) pair if complex)
-        if (i64) return c64 ? numeric_typed<T, int64_t, int64_t>(h, *p, *C, a)
-                            : numeric_typed<T, int64_t, int32_t>(h, *p, *C, a);
-        return c64 ? numeric_typed<T, int32_t, int64_t>(h, *p, *C, a)
-                   : numeric_typed<T, int32_t, int32_t>(h, *p, *C, a);
+        return dispatch_index(p->A.indptr_type, C->indptr_type, [&](auto ip, auto cp) {
+            return numeric_typed<T, decltype(ip), decltype(cp)>(h, *p, *C, a);
+        });
     });
 }
 
@@ -1899,7 +2251,7 @@ static spg_status_t tiles_supported(spg_handle_t h, spg_plan_t p) {
     if (!p) return SPG_STATUS_INVALID_VALUE;
     if (!p->use_tile || tile_chunks(*p) != 1 || p->alg1_fused) return SPG_STATUS_NOT_SUPPORTED;
     if (p->tidx_built) return SPG_STATUS_SUCCESS;
-    return p->A.indptr_type == SPG_INDEX_64I ? tile_build_index<int64_t>(h, *p) : tile_build_index<int32_t>(h, *p);
+    return dispatch_index(p->A.indptr_type, [&](auto ip) { return tile_build_index<decltype(ip)>(h, *p); });
 }
 
 spg_status_t spg_tile_value_offsets(spg_handle_t h, spg_plan_t p, int64_t* offsets, int64_t capacity) {
@@ -1933,18 +2285,16 @@ spg_status_t spg_tile_values(spg_handle_t h, spg_plan_t p, void* tm) {
     if (!tm && p->B.nnz > 0) return SPG_STATUS_INVALID_VALUE;
     if (p->B.nnz > 0 && !p->B.values) return SPG_STATUS_INVALID_VALUE;
     if (p->B.rows == 0 || p->B.nnz == 0) return SPG_STATUS_SUCCESS;
-    const bool i64 = p->A.indptr_type == SPG_INDEX_64I;
     return dispatch_value(p->A.value_type, [&](auto tag) {
         using T = decltype(tag);
-        auto go = [&](auto ip) {
+        return dispatch_index(p->A.indptr_type, [&](auto ip) {
             using IP = decltype(ip);
             timed_launch(h, SPG_PHASE_LAYOUT, k_bt_pack<T, IP, 2>, dim3((unsigned)grid_for(p->B.rows, 4)), dim3(256),
                          p->B.rows, (const IP*)p->B.indptr, (const int32_t*)p->B.indices, (const T*)p->B.values,
                          p->tws, (const int32_t*)p->tptr, (uint32_t*)p->brec, p->B.nnz, (T*)tm, p->rgs);
-        };
-        if (i64) go(int64_t{}); else go(int32_t{});
-        SPG_LAUNCHED(h);
-        return SPG_STATUS_SUCCESS;
+            SPG_LAUNCHED(h);
+            return SPG_STATUS_SUCCESS;
+        });
     });
 }
 
@@ -1965,15 +2315,15 @@ spg_status_t spg_numeric_tiles(spg_handle_t h, spg_plan_t p, const void* alpha, 
     if (p->nnzC > 0 && (!C->indices || !C->values)) return SPG_STATUS_INVALID_VALUE;
     if (p->B.nnz > 0 && !tm) return SPG_STATUS_INVALID_VALUE;
     if (p->nnzC == 0 || g0 == g1) return SPG_STATUS_SUCCESS;
-    const bool i64 = p->A.indptr_type == SPG_INDEX_64I;
     return dispatch_value(p->A.value_type, [&](auto tag) {
         using T = decltype(tag);
         T a;
         std::memcpy(&a, alpha, sizeof(T));
         // value tiles [g0, g1) = numeric tiles [g0 * RG, min(G, g1 * RG))
         const int64_t t0 = g0 << p->rgs, t1 = std::min<int64_t>(p->G, g1 << p->rgs);
-        return i64 ? tile_numeric<T, int64_t>(h, *p, (int32_t*)C->indices, (T*)C->values, a, t0, t1, (const T*)tm)
-                   : tile_numeric<T, int32_t>(h, *p, (int32_t*)C->indices, (T*)C->values, a, t0, t1, (const T*)tm);
+        return dispatch_index(p->A.indptr_type, [&](auto ip) {
+            return tile_numeric<T, decltype(ip)>(h, *p, (int32_t*)C->indices, (T*)C->values, a, t0, t1, (const T*)tm);
+        });
     });
 }
 
@@ -1987,7 +2337,6 @@ spg_status_t spg_spmv(spg_handle_t h, const spg_csr_t* A, const void* x, const v
     if (A->rows == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    const bool i64 = A->indptr_type == SPG_INDEX_64I;
     return dispatch_value(A->value_type, [&](auto tag) {
         using T = decltype(tag);
         T al, be;
@@ -1995,16 +2344,14 @@ spg_status_t spg_spmv(spg_handle_t h, const spg_csr_t* A, const void* x, const v
         std::memcpy(&be, beta, sizeof(T));
         const unsigned grid = (unsigned)grid_for(A->rows, SPMV_WPB * WAVE);
         PhaseTimer pt(h, SPG_PHASE_SPMV);
-        if (i64)
-            hipLaunchKernelGGL((k_spmv<T, int64_t>), dim3(grid), dim3(SPMV_WPB * WAVE), 0, h->stream, A->rows,
-                               (const int64_t*)A->indptr, (const int32_t*)A->indices, (const T*)A->values,
+        return dispatch_index(A->indptr_type, [&](auto ip) {
+            using IP = decltype(ip);
+            hipLaunchKernelGGL((k_spmv<T, IP>), dim3(grid), dim3(SPMV_WPB * WAVE), 0, h->stream, A->rows,
+                               (const IP*)A->indptr, (const int32_t*)A->indices, (const T*)A->values,
                                (const T*)x, al, be, (T*)y);
-        else
-            hipLaunchKernelGGL((k_spmv<T, int32_t>), dim3(grid), dim3(SPMV_WPB * WAVE), 0, h->stream, A->rows,
-                               (const int32_t*)A->indptr, (const int32_t*)A->indices, (const T*)A->values,
-                               (const T*)x, al, be, (T*)y);
-        SPG_LAUNCHED(h);
-        return SPG_STATUS_SUCCESS;
+            SPG_LAUNCHED(h);
+            return SPG_STATUS_SUCCESS;
+        });
     });
 }
 
@@ -2021,123 +2368,16 @@ spg_status_t spg_spmm(spg_handle_t h, const spg_csr_t* A, const spg_dense_t* B, 
     if (A->rows == 0 || B->cols == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    const bool i64 = A->indptr_type == SPG_INDEX_64I;
     return dispatch_value(A->value_type, [&](auto tag) {
         using T = decltype(tag);
         T al, be;
         std::memcpy(&al, alpha, sizeof(T));
         std::memcpy(&be, beta, sizeof(T));
-        return i64 ? spmm_launch<T, int64_t>(h, *A, *B, al, be, *C) : spmm_launch<T, int32_t>(h, *A, *B, al, be, *C);
+        return dispatch_index(A->indptr_type, [&](auto ip) {
+            return spmm_launch<T, decltype(ip)>(h, *A, *B, al, be, *C);
+        });
     });
 }
-
-// ----------------------------------------------------------------------------- spg_csr2csc
-extern "C++" {
-namespace {
-
-// Workspace carve of spg_csr2csc (offsets from the 256-byte aligned base).
-struct TrLayout {
-    int passes = 1;            // 8-bit digit passes: the bytes of cols - 1 (at least one)
-    int64_t chunks = 0;        // wave chunks of TR_CHUNK entries
-    int nbuf = 0;              // ping-pong record buffers the passes need (0, 1 or 2)
-    size_t scalars = 0, status = 0, table = 0, skeys = 0, buf[2] = {0, 0};
-    size_t keys = 0, rowids = 0, pos = 0;   // inside one record buffer
-    size_t total = 0;          // bytes to ask for (256 of slack for the base alignment)
-};
-
-TrLayout tr_layout(const spg_csr_t& A) {
-    TrLayout L;
-    const size_t ips = A.indptr_type == SPG_INDEX_64I ? 8 : 4;
-    const uint64_t top = A.cols > 0 ? (uint64_t)(A.cols - 1) : 0;
-    L.passes = top >= (1ull << 24) ? 4 : top >= (1ull << 16) ? 3 : top >= (1ull << 8) ? 2 : 1;
-    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
-    L.nbuf = std::min(L.passes - 1, 2);
-    size_t off = 0;
-    L.scalars = off;
-    off += align_up(16 * sizeof(int64_t));
-    L.status = off;
-    off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(TR_RADIX * L.chunks) + 1));
-    L.table = off;
-    off += align_up(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
-    L.skeys = off;   // the sorted columns (the last pass -> k_tr_indptr)
-    off += align_up(sizeof(int32_t) * (size_t)A.nnz);
-    L.keys = 0;
-    L.rowids = align_up(sizeof(int32_t) * (size_t)A.nnz);
-    L.pos = 2 * L.rowids;
-    const size_t rec = L.pos + align_up(ips * (size_t)A.nnz);
-    for (int b = 0; b < L.nbuf; ++b) {
-        L.buf[b] = off;
-        off += rec;
-    }
-    L.total = off + 256;
-    return L;
-}
-
-template <typename IP>
-spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrLayout& L, char* ws) {
-    const int64_t nnz = A.nnz, chunks = L.chunks;
-    int64_t* scal = (int64_t*)(ws + L.scalars);
-    unsigned long long* status = (unsigned long long*)(ws + L.status);
-    IP* table = (IP*)(ws + L.table);
-    IP* ATp = (IP*)AT.indptr;
-    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
-    const int32_t* kin = (const int32_t*)A.indices;
-    const int32_t* rin = nullptr;
-    const IP* pin = nullptr;
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    for (int p = 0; p < L.passes; ++p) {
-        const int shift = 8 * p;
-        const bool first = p == 0, last = p == L.passes - 1;
-        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP>, grid, block, nnz, chunks, TrKeys{kin}, shift, table);
-        SPG_LAUNCHED(h);
-        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
-        char* out = last ? nullptr : ws + L.buf[p & 1];
-        int32_t* kout = last ? (int32_t*)(ws + L.skeys) : (int32_t*)(out + L.keys);
-        int32_t* rout = last ? nullptr : (int32_t*)(out + L.rowids);
-        IP* pout = last ? nullptr : (IP*)(out + L.pos);
-        if (!last) {
-            using V = uint32_t;   // (no value is touched before the last pass)
-            if (first)
-                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, false>, grid, block, nnz, chunks, shift,
-                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
-                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
-            else
-                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, false>, grid, block, nnz, chunks, shift,
-                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
-                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
-        } else {
-            auto run_last = [&](auto vtag) {
-                using V = decltype(vtag);
-                if (first)
-                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, true>, grid, block, nnz, chunks,
-                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
-                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
-                else
-                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, true>, grid, block, nnz, chunks,
-                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
-                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
-            };
-            switch (vbytes(A.value_type)) {
-                case 4: run_last(TrBits<4>::type{}); break;
-                case 8: run_last(TrBits<8>::type{}); break;
-                default: run_last(TrBits<16>::type{}); break;
-            }
-        }
-        SPG_LAUNCHED(h);
-        kin = kout;
-        rin = rout;
-        pin = pout;
-    }
-    // (kin: the sorted columns the last pass left)
-    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP, IP>, dim3(pgrid), dim3(256), nnz, A.cols, TrKeys{kin}, ATp,
-                 (const IP*)nullptr);
-    SPG_LAUNCHED(h);
-    return SPG_STATUS_SUCCESS;
-}
-
-}  // namespace
-}  // extern "C++"
 
 spg_status_t spg_csr2csc(spg_handle_t h, const spg_csr_t* A, spg_csr_t* AT, size_t* workspace_bytes,
                          void* workspace) {
@@ -2150,108 +2390,18 @@ spg_status_t spg_csr2csc(spg_handle_t h, const spg_csr_t* A, spg_csr_t* AT, size
     if (AT->value_type != A->value_type || AT->indptr_type != A->indptr_type) return SPG_STATUS_INVALID_VALUE;
     if (A->nnz > 0 && (A->rows == 0 || A->cols == 0)) return SPG_STATUS_INVALID_VALUE;
     const TrLayout L = tr_layout(*A);
-    if (!workspace) {   // size query: host arithmetic only
-        *workspace_bytes = L.total;
-        return SPG_STATUS_SUCCESS;
-    }
-    if (*workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
     if (!AT->indptr || (A->nnz > 0 && (!AT->indices || !AT->values))) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    const bool i64 = A->indptr_type == SPG_INDEX_64I;
     if (A->nnz == 0) {   // an all-zero row pointer
-        SPG_HIP(h, hipMemsetAsync(AT->indptr, 0, (i64 ? 8 : 4) * (size_t)(A->cols + 1), h->stream));
+        SPG_HIP(h, hipMemsetAsync(AT->indptr, 0, index_bytes(A->indptr_type) * (size_t)(A->cols + 1), h->stream));
         return SPG_STATUS_SUCCESS;
     }
-    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    return i64 ? tr_run<int64_t>(h, *A, *AT, L, ws) : tr_run<int32_t>(h, *A, *AT, L, ws);
+    return dispatch_index(A->indptr_type, [&](auto ip) {
+        return tr_run<decltype(ip)>(h, *A, *AT, L, ws_base(workspace));
+    });
 }
-
-// ----------------------------------------------------------------------------- spg_csrgeam
-extern "C++" {
-namespace {
-
-// Workspace carve of spg_csrgeam_nnz / spg_csrgeam (offsets from the 256-byte aligned base).
-struct GmLayout {
-    int64_t chunksA = 0, chunksB = 0;   // wave chunks of GM_CHUNK entries
-    size_t scalars = 0;                 // 16 int64: [0] a scan's total, [1] its overflow flag
-    size_t status_b = 0, status_r = 0;  // look-back words of the scan over B's entries / over the rows
-    size_t S = 0;                       // nnz(B) + 1 IP: B-only marks, scanned in place (kept for the value pass)
-    size_t cnt = 0;                     // rows + 1 int64: entries per row of C
-    size_t total = 0;                   // bytes to ask for (256 of slack for the base alignment)
-};
-
-GmLayout gm_layout(const spg_csr_t& A, const spg_csr_t& B) {
-    GmLayout L;
-    const size_t ips = A.indptr_type == SPG_INDEX_64I ? 8 : 4;
-    L.chunksA = (A.nnz + GM_CHUNK - 1) / GM_CHUNK;
-    L.chunksB = (B.nnz + GM_CHUNK - 1) / GM_CHUNK;
-    size_t off = 0;
-    L.scalars = off;
-    off += align_up(16 * sizeof(int64_t));
-    L.status_b = off;
-    off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(B.nnz) + 1));
-    L.status_r = off;
-    off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(A.rows) + 1));
-    L.S = off;
-    off += align_up(ips * ((size_t)B.nnz + 1));
-    L.cnt = off;
-    off += align_up(sizeof(int64_t) * ((size_t)A.rows + 1));
-    L.total = off + 256;
-    return L;
-}
-
-// what both entry points ask of the operands
-spg_status_t gm_check(const spg_csr_t* A, const spg_csr_t* B) {
-    if (!A || !B) return SPG_STATUS_INVALID_VALUE;
-    spg_status_t st = check_csr(A);
-    if (st || (st = check_csr(B))) return st;
-    if (A->rows != B->rows || A->cols != B->cols || A->value_type != B->value_type ||
-        A->indptr_type != B->indptr_type)
-        return SPG_STATUS_INVALID_VALUE;
-    return SPG_STATUS_SUCCESS;
-}
-
-template <typename IP, typename CP>
-spg_status_t gm_structure(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, const GmLayout& L, char* ws,
-                          CP* Cp, int64_t* nnzC) {
-    int64_t* scal = (int64_t*)(ws + L.scalars);
-    IP* S = (IP*)(ws + L.S);
-    int64_t* cnt = (int64_t*)(ws + L.cnt);
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    if (B.nnz > 0) {
-        timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_mark<IP>, dim3((unsigned)grid_for(L.chunksB, GM_WPB)),
-                     dim3(GM_WPB * WAVE), A.rows, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices,
-                     (const IP*)B.indptr, (const int32_t*)B.indices, S);
-        SPG_LAUNCHED(h);
-    }
-    if ((st = launch_scan<IP, IP>(h, B.nnz, S, S, (unsigned long long*)(ws + L.status_b), scal, true))) return st;
-    const unsigned cgrid = (unsigned)std::min<int64_t>(grid_for(A.rows, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_count<IP>, dim3(cgrid), dim3(256), A.rows, (const IP*)A.indptr,
-                 (const IP*)B.indptr, (const IP*)S, cnt);
-    SPG_LAUNCHED(h);
-    if ((st = launch_scan<CP, int64_t>(h, A.rows, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
-        return st;
-    int64_t sc[2] = {0, 0};
-    if ((st = read_scalars(h, scal, 2, sc))) return st;
-    *nnzC = sc[0];
-    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
-}
-
-template <typename IP, typename CP, typename T>
-spg_status_t gm_values(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, spg_csr_t& C, const GmLayout& L,
-                       char* ws, T alpha, T beta) {
-    timed_launch(h, SPG_PHASE_NUMERIC, k_geam_fill<IP, CP, T>,
-                 dim3((unsigned)grid_for(L.chunksA + L.chunksB, GM_WPB)), dim3(GM_WPB * WAVE), A.rows, A.nnz,
-                 L.chunksA, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices, (const T*)A.values,
-                 (const IP*)B.indptr, (const int32_t*)B.indices, (const T*)B.values, (const IP*)(ws + L.S),
-                 (const CP*)C.indptr, (int32_t*)C.indices, (T*)C.values, alpha, beta);
-    SPG_LAUNCHED(h);
-    return SPG_STATUS_SUCCESS;
-}
-
-}  // namespace
-}  // extern "C++"
 
 spg_status_t spg_csrgeam_nnz(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, void* C_indptr,
                              spg_index_t C_indptr_type, int64_t* nnzC, size_t* workspace_bytes, void* workspace) {
@@ -2261,25 +2411,19 @@ spg_status_t spg_csrgeam_nnz(spg_handle_t h, const spg_csr_t* A, const spg_csr_t
     if (st) return st;
     if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     const GmLayout L = gm_layout(*A, *B);
-    if (!workspace) {   // size query: host arithmetic only
-        *workspace_bytes = L.total;
-        return SPG_STATUS_SUCCESS;
-    }
-    if (*workspace_bytes < L.total || !C_indptr) return SPG_STATUS_INVALID_VALUE;
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
+    if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    const bool c64 = C_indptr_type == SPG_INDEX_64I;
     if (A->rows == 0) {   // the one entry of an empty row pointer
-        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, c64 ? 8 : 4, h->stream));
+        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type), h->stream));
         *nnzC = 0;
         return SPG_STATUS_SUCCESS;
     }
-    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    if (A->indptr_type == SPG_INDEX_64I)
-        return c64 ? gm_structure<int64_t, int64_t>(h, *A, *B, L, ws, (int64_t*)C_indptr, nnzC)
-                   : gm_structure<int64_t, int32_t>(h, *A, *B, L, ws, (int32_t*)C_indptr, nnzC);
-    return c64 ? gm_structure<int32_t, int64_t>(h, *A, *B, L, ws, (int64_t*)C_indptr, nnzC)
-               : gm_structure<int32_t, int32_t>(h, *A, *B, L, ws, (int32_t*)C_indptr, nnzC);
+    return dispatch_index(A->indptr_type, C_indptr_type, [&](auto ip, auto cp) {
+        using CP = decltype(cp);
+        return gm_structure<decltype(ip), CP>(h, *A, *B, L, ws_base(workspace), (CP*)C_indptr, nnzC);
+    });
 }
 
 spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, const void* beta,
@@ -2297,205 +2441,16 @@ spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, 
     if (A->rows == 0 || C->nnz == 0 || A->nnz + B->nnz == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const bool i64 = A->indptr_type == SPG_INDEX_64I, c64 = C->indptr_type == SPG_INDEX_64I;
     return dispatch_value(A->value_type, [&](auto tag) {
         using T = decltype(tag);
         T al, be;
         std::memcpy(&al, alpha, sizeof(T));
         std::memcpy(&be, beta, sizeof(T));
-        if (i64)
-            return c64 ? gm_values<int64_t, int64_t, T>(h, *A, *B, *C, L, ws, al, be)
-                       : gm_values<int64_t, int32_t, T>(h, *A, *B, *C, L, ws, al, be);
-        return c64 ? gm_values<int32_t, int64_t, T>(h, *A, *B, *C, L, ws, al, be)
-                   : gm_values<int32_t, int32_t, T>(h, *A, *B, *C, L, ws, al, be);
+        return dispatch_index(A->indptr_type, C->indptr_type, [&](auto ip, auto cp) {
+            return gm_values<decltype(ip), decltype(cp), T>(h, *A, *B, *C, L, ws_base(workspace), al, be);
+        });
     });
 }
-
-// ----------------------------------------------------------------------------- spg_canonicalize
-extern "C++" {
-namespace {
-
-// bits of an index below `extent`: the bits of extent - 1 (at least one)
-inline int index_bits(int64_t extent) {
-    int b = 1;
-    while (b < 63 && ((int64_t)1 << b) < extent) ++b;
-    return b;
-}
-
-// Workspace carve of spg_canonicalize_nnz / spg_canonicalize (offsets from the 256-byte aligned
-// base).  The sorted records stay in buf[passes & 1] and the scanned marks in `kept` for the
-// value call.
-struct CnLayout {
-    bool sum = false, drop = false;
-    bool marks = false;         // SUM or DROP_ZEROS: kept[] exists
-    int cbits = 1, rbits = 1;   // key = row << cbits | column
-    bool k64 = false;           // the key takes 64 bits
-    int shift0 = 0;             // the first digit's shift: 0, or cbits when only the rows are sorted (COO, no op)
-    int passes = 0;             // 0: CSR input with DROP_ZEROS alone, no sort (the entries are their own records)
-    int64_t chunks = 0;         // wave chunks of TR_CHUNK entries
-    size_t scalars = 0;         // 16 int64: [0] a scan's total
-    size_t status_t = 0, status_k = 0;   // look-back words of the table scans / of the scan over kept[]
-    size_t table = 0;           // 256 * chunks + 1 IP: a pass's digit histogram, scanned in place
-    size_t kept = 0;            // nnz + 1 IP: the kept marks, scanned in place
-    size_t buf[2] = {0, 0};     // ping-pong record buffers (k_cn_pack writes buf[0])
-    size_t total = 0;           // bytes to ask for (256 of slack for the base alignment)
-};
-
-CnLayout cn_layout(const spg_csr_t& A, bool coo, unsigned ops) {
-    CnLayout L;
-    const size_t ips = A.indptr_type == SPG_INDEX_64I ? 8 : 4;
-    const size_t nnz = (size_t)A.nnz;
-    L.sum = (ops & SPG_CANON_SUM) != 0;
-    L.drop = (ops & SPG_CANON_DROP_ZEROS) != 0;
-    L.marks = L.sum || L.drop;
-    const bool sort = L.sum || (ops & SPG_CANON_SORT) != 0;
-    L.cbits = index_bits(A.cols);
-    L.rbits = index_bits(A.rows);
-    L.k64 = L.cbits + L.rbits > 32;
-    L.shift0 = sort ? 0 : L.cbits;
-    L.passes = sort || coo ? (L.cbits + L.rbits - L.shift0 + 7) / 8 : 0;
-    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
-    size_t off = 0;
-    L.scalars = off;
-    off += align_up(16 * sizeof(int64_t));
-    if (L.passes) {
-        L.status_t = off;
-        off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(TR_RADIX * L.chunks) + 1));
-        L.table = off;
-        off += align_up(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
-    }
-    if (L.marks) {
-        L.status_k = off;
-        off += align_up(sizeof(unsigned long long) * (size_t)(scan_tiles(A.nnz) + 1));
-        L.kept = off;
-        off += align_up(ips * (nnz + 1));
-    }
-    const size_t rec = align_up((ips == 4 && !L.k64 ? 8 : 16) * nnz);   // sizeof(CnRec<IP, K>)
-    for (int b = 0; b < (L.passes ? 2 : 0); ++b) {
-        L.buf[b] = off;
-        off += rec;
-    }
-    L.total = off + 256;
-    return L;
-}
-
-// what both entry points ask of the input
-spg_status_t cn_check(const spg_csr_t* A, const int32_t* coo_rows, unsigned ops) {
-    if (!A) return SPG_STATUS_INVALID_VALUE;
-    if (A->rows < 0 || A->cols < 0 || A->nnz < 0) return SPG_STATUS_INVALID_VALUE;
-    if (A->cols > 2147483647LL || A->rows > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;   // int32 ids
-    if (A->indptr_type != SPG_INDEX_32I && A->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
-    if (A->value_type != SPG_R_32F && A->value_type != SPG_R_64F && A->value_type != SPG_C_32F &&
-        A->value_type != SPG_C_64F)
-        return SPG_STATUS_NOT_SUPPORTED;
-    if (A->indptr_type == SPG_INDEX_32I && A->nnz > 2147483647LL) return SPG_STATUS_INVALID_VALUE;
-    if (ops & ~(unsigned)(SPG_CANON_SORT | SPG_CANON_SUM | SPG_CANON_DROP_ZEROS)) return SPG_STATUS_INVALID_VALUE;
-    if (!coo_rows && (!A->indptr || ops == 0)) return SPG_STATUS_INVALID_VALUE;   // CSR: something to do
-    if (A->nnz > 0 && (!A->indices || !A->values)) return SPG_STATUS_INVALID_VALUE;
-    if (A->nnz > 0 && (A->rows == 0 || A->cols == 0)) return SPG_STATUS_INVALID_VALUE;
-    return SPG_STATUS_SUCCESS;
-}
-
-// the sorted records the structure call left (nullptr: unsorted, A's entries themselves)
-template <typename IP, typename K>
-const CnRec<IP, K>* cn_records(const CnLayout& L, char* ws) {
-    return L.passes ? (const CnRec<IP, K>*)(ws + L.buf[L.passes & 1]) : nullptr;
-}
-
-template <typename IP, typename K>
-spg_status_t cn_sort(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows, const CnLayout& L, char* ws) {
-    using Rec = CnRec<IP, K>;
-    static_assert(sizeof(Rec) == (sizeof(IP) + sizeof(K) == 8 ? 8 : 16), "cn_layout's record size");
-    const int64_t nnz = A.nnz, chunks = L.chunks;
-    int64_t* scal = (int64_t*)(ws + L.scalars);
-    unsigned long long* status = (unsigned long long*)(ws + L.status_t);
-    IP* table = (IP*)(ws + L.table);
-    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
-    auto pack = coo_rows ? k_cn_pack<IP, K, CN_FROM_COO> : k_cn_pack<IP, K, CN_FROM_CSR>;
-    timed_launch(h, SPG_PHASE_LAYOUT, pack, grid, block, nnz, chunks, L.cbits, (const int32_t*)A.indices, coo_rows,
-                 (const IP*)A.indptr, A.rows, (Rec*)(ws + L.buf[0]));
-    SPG_LAUNCHED(h);
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    for (int p = 0; p < L.passes; ++p) {
-        const int shift = L.shift0 + 8 * p;
-        const Rec* in = (const Rec*)(ws + L.buf[p & 1]);
-        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP, CnKeys<IP, K>>, grid, block, nnz, chunks,
-                     CnKeys<IP, K>{in, 0}, shift, table);
-        SPG_LAUNCHED(h);
-        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<IP, K>, grid, block, nnz, chunks, shift, in,
-                     (const IP*)table, (Rec*)(ws + L.buf[(p + 1) & 1]));
-        SPG_LAUNCHED(h);
-    }
-    return SPG_STATUS_SUCCESS;
-}
-
-template <typename IP, typename CP, typename K>
-spg_status_t cn_structure(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows, const CnLayout& L, char* ws,
-                          CP* Cp, int64_t* nnzC) {
-    const int64_t nnz = A.nnz;
-    int64_t* scal = (int64_t*)(ws + L.scalars);
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    if (L.passes && (st = cn_sort<IP, K>(h, A, coo_rows, L, ws))) return st;
-    const CnRec<IP, K>* rec = cn_records<IP, K>(L, ws);
-    IP* kept = L.marks ? (IP*)(ws + L.kept) : nullptr;
-    if (L.marks) {
-        const dim3 grid((unsigned)grid_for(nnz, CN_BLOCK)), block(CN_BLOCK);
-        if (!L.drop) {   // (no value is read)
-            timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_mark<IP, K, uint32_t, true, false>, grid, block, nnz, rec,
-                         (const uint32_t*)nullptr, kept);
-        } else {
-            st = dispatch_value(A.value_type, [&](auto tag) {
-                using T = decltype(tag);
-                auto mark = L.sum ? k_cn_mark<IP, K, T, true, true> : k_cn_mark<IP, K, T, false, true>;
-                timed_launch(h, SPG_PHASE_SYMBOLIC, mark, grid, block, nnz, rec, (const T*)A.values, kept);
-                return SPG_STATUS_SUCCESS;
-            });
-            if (st) return st;
-        }
-        SPG_LAUNCHED(h);
-        if ((st = launch_scan<IP, IP>(h, nnz, kept, kept, (unsigned long long*)(ws + L.status_k), scal, true)))
-            return st;
-    }
-    if (L.passes) {   // off the sorted keys' rows
-        const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.rows + 1, 256), 1 << 20);
-        timed_launch(h, SPG_PHASE_SYMBOLIC, k_tr_indptr<IP, CP, CnKeys<IP, K>>, dim3(pgrid), dim3(256), nnz, A.rows,
-                     CnKeys<IP, K>{rec, L.cbits}, Cp, (const IP*)kept);
-    } else {
-        timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_indptr<IP, CP>, dim3((unsigned)grid_for(A.rows + 1, CN_BLOCK)),
-                     dim3(CN_BLOCK), A.rows, (const IP*)A.indptr, (const IP*)kept, Cp);
-    }
-    SPG_LAUNCHED(h);
-    *nnzC = nnz;
-    if (L.marks) {
-        int64_t total = 0;
-        if ((st = read_scalars(h, scal, 1, &total))) return st;
-        *nnzC = total;
-    }
-    return (sizeof(CP) == 4 && *nnzC > 2147483647LL) ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
-}
-
-template <typename IP, typename K, typename T, bool SUM>
-spg_status_t cn_values(spg_handle_t h, const spg_csr_t& A, spg_csr_t& C, const CnLayout& L, char* ws) {
-    const K cmask = (K)(((uint64_t)1 << L.cbits) - 1);
-    timed_launch(h, SPG_PHASE_NUMERIC, k_cn_fill<IP, K, T, SUM>, dim3((unsigned)grid_for(A.nnz, CN_BLOCK)),
-                 dim3(CN_BLOCK), A.nnz, cn_records<IP, K>(L, ws), cmask, (const int32_t*)A.indices,
-                 (const T*)A.values, L.marks ? (const IP*)(ws + L.kept) : (const IP*)nullptr, (int32_t*)C.indices,
-                 (T*)C.values);
-    SPG_LAUNCHED(h);
-    return SPG_STATUS_SUCCESS;
-}
-
-// f(IP{}, K{}) with the position and key types of this input
-template <typename F>
-spg_status_t cn_dispatch(const spg_csr_t& A, const CnLayout& L, F&& f) {
-    if (A.indptr_type == SPG_INDEX_64I) return L.k64 ? f(int64_t(0), uint64_t(0)) : f(int64_t(0), uint32_t(0));
-    return L.k64 ? f(int32_t(0), uint64_t(0)) : f(int32_t(0), uint32_t(0));
-}
-
-}  // namespace
-}  // extern "C++"
 
 spg_status_t spg_canonicalize_nnz(spg_handle_t h, const spg_csr_t* A, const int32_t* coo_rows, unsigned ops,
                                   void* C_indptr, spg_index_t C_indptr_type, int64_t* nnzC,
@@ -2506,25 +2461,21 @@ spg_status_t spg_canonicalize_nnz(spg_handle_t h, const spg_csr_t* A, const int3
     if (st) return st;
     if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     const CnLayout L = cn_layout(*A, coo_rows != nullptr, ops);
-    if (!workspace) {   // size query: host arithmetic only
-        *workspace_bytes = L.total;
-        return SPG_STATUS_SUCCESS;
-    }
-    if (*workspace_bytes < L.total || !C_indptr) return SPG_STATUS_INVALID_VALUE;
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
+    if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    const bool c64 = C_indptr_type == SPG_INDEX_64I;
     if (A->rows == 0 || A->nnz == 0) {   // an all-zero row pointer
-        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, (c64 ? 8 : 4) * (size_t)(A->rows + 1), h->stream));
+        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type) * (size_t)(A->rows + 1), h->stream));
         *nnzC = 0;
         return SPG_STATUS_SUCCESS;
     }
-    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     return cn_dispatch(*A, L, [&](auto ip, auto key) {
-        using IP = decltype(ip);
-        using K = decltype(key);
-        return c64 ? cn_structure<IP, int64_t, K>(h, *A, coo_rows, L, ws, (int64_t*)C_indptr, nnzC)
-                   : cn_structure<IP, int32_t, K>(h, *A, coo_rows, L, ws, (int32_t*)C_indptr, nnzC);
+        return dispatch_index(C_indptr_type, [&](auto cp) {
+            using CP = decltype(cp);
+            return cn_structure<decltype(ip), CP, decltype(key)>(h, *A, coo_rows, L, ws_base(workspace),
+                                                                 (CP*)C_indptr, nnzC);
+        });
     });
 }
 
@@ -2545,7 +2496,7 @@ spg_status_t spg_canonicalize(spg_handle_t h, const spg_csr_t* A, const int32_t*
     if (C->nnz == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    char* ws = ws_base(workspace);
     return cn_dispatch(*A, L, [&](auto ip, auto key) {
         using IP = decltype(ip);
         using K = decltype(key);
@@ -2599,14 +2550,13 @@ spg_status_t spg_cols16_split(spg_handle_t h, const spg_csr_t* M, uint32_t* bloc
     SPG_HIP(h, dg_.err);
     const int nb1 = cols16_nb1(M);
     const dim3 g((unsigned)grid_for(M->rows, 4)), b(256);
-    if (M->indptr_type == SPG_INDEX_64I)
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cols16_split<int64_t>, g, b, M->rows, (const int64_t*)M->indptr,
+    return dispatch_index(M->indptr_type, [&](auto ip) {
+        using IP = decltype(ip);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_cols16_split<IP>, g, b, M->rows, (const IP*)M->indptr,
                      (const int32_t*)M->indices, nb1, block_starts, lo16);
-    else
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cols16_split<int32_t>, g, b, M->rows, (const int32_t*)M->indptr,
-                     (const int32_t*)M->indices, nb1, block_starts, lo16);
-    SPG_LAUNCHED(h);
-    return SPG_STATUS_SUCCESS;
+        SPG_LAUNCHED(h);
+        return SPG_STATUS_SUCCESS;
+    });
 }
 
 spg_status_t spg_cols16_join(spg_handle_t h, spg_csr_t* M, const uint32_t* block_starts, const uint16_t* lo16) {
@@ -2618,14 +2568,13 @@ spg_status_t spg_cols16_join(spg_handle_t h, spg_csr_t* M, const uint32_t* block
     SPG_HIP(h, dg_.err);
     const int nb1 = cols16_nb1(M);
     const dim3 g((unsigned)grid_for(M->rows, 4)), b(256);
-    if (M->indptr_type == SPG_INDEX_64I)
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cols16_join<int64_t>, g, b, M->rows, (const int64_t*)M->indptr, nb1,
-                     block_starts, lo16, (int32_t*)M->indices);
-    else
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cols16_join<int32_t>, g, b, M->rows, (const int32_t*)M->indptr, nb1,
-                     block_starts, lo16, (int32_t*)M->indices);
-    SPG_LAUNCHED(h);
-    return SPG_STATUS_SUCCESS;
+    return dispatch_index(M->indptr_type, [&](auto ip) {
+        using IP = decltype(ip);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_cols16_join<IP>, g, b, M->rows, (const IP*)M->indptr, nb1, block_starts,
+                     lo16, (int32_t*)M->indices);
+        SPG_LAUNCHED(h);
+        return SPG_STATUS_SUCCESS;
+    });
 }
 
 spg_status_t spg_validate_csr(spg_handle_t h, const spg_csr_t* M, int* is_canonical) {
@@ -2638,9 +2587,17 @@ spg_status_t spg_validate_csr(spg_handle_t h, const spg_csr_t* M, int* is_canoni
     if ((st = ensure_scratch(h, 256))) return st;
     int* flags = (int*)h->scratch;
     SPG_HIP(h, hipMemsetAsync(flags, 0, 2 * sizeof(int), h->stream));
-    st = M->indptr_type == SPG_INDEX_64I ? validate_typed<int64_t>(h, *M, flags)
-                                         : validate_typed<int32_t>(h, *M, flags);
-    if (st) return st;
+    if (M->rows > 0) {
+        PhaseTimer pt(h, SPG_PHASE_VALIDATE);
+        st = dispatch_index(M->indptr_type, [&](auto ip) {
+            using IP = decltype(ip);
+            hipLaunchKernelGGL(k_validate<IP>, dim3((unsigned)grid_for(M->rows, BLOCK)), dim3(BLOCK), 0, h->stream,
+                               M->rows, M->cols, M->nnz, (const IP*)M->indptr, (const int32_t*)M->indices, flags);
+            SPG_LAUNCHED(h);
+            return SPG_STATUS_SUCCESS;
+        });
+        if (st) return st;
+    }
     SPG_HIP(h, hipMemcpyAsync(h->pinned, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     SPG_HIP(h, hipStreamSynchronize(h->stream));
     const int* f = (const int*)h->pinned;

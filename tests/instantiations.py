@@ -46,7 +46,9 @@ kernels' seams:
   the 640-product row has 640 distinct output columns, more than one stage window of
   row_write_staged (W = offsetof(RowLds, lb_gw) / (sizeof(T) + 4): fp64 517 with int32 row
   pointers and 602 with int64, complex64 the same, complex128 387; fp32 776 / 904, which no row
-  of <= 640 products can exceed), and touches columns 0 and n - 1.
+  of <= 640 products can exceed), and touches columns 0 and n - 1.  short64 is the same structure
+  without the 65-entry row: k_short's single pass (ALG1) refuses that row and no other, so only
+  there does the C it writes stay.
 
 Planner margins (plan(): value / threshold of every inequality that decides a case, measured on
 the generated inputs; test_instantiations_cpu.py asserts each is at least MARGIN away from 1):
@@ -56,6 +58,9 @@ the generated inputs; test_instantiations_cpu.py asserts each is at least MARGIN
   short-f64, short-kshort-f64:
       short: avgA <= 48: 10.14 / 48 = 0.21
       short: avgA*avgB <= 400: 78.97 / 400 = 0.20
+  short64-kshort-f64:
+      short: avgA <= 48: 9.761 / 48 = 0.20
+      short: avgA*avgB <= 400: 75.98 / 400 = 0.19
   short-c64:
       short: avgA <= 48: 10.05 / 48 = 0.21
       short: avgA*avgB <= 400: 78.23 / 400 = 0.20
@@ -179,6 +184,9 @@ def a_lengths(dname):
 Struct = namedtuple("Struct", "kind k n avg_a avg_b tw caps rg")
 STRUCTS = {
     "short": Struct("short", 2048, 2048, 8.0, 8.0, 0, (), False),
+    # `short` without its 65-entry A row (an ordinary fill row in its place): no row k_short's
+    # single pass refuses (it takes rows of <= 64 entries whatever their products)
+    "short64": Struct("short", 2048, 2048, 8.0, 8.0, 0, (), False),
     "general": Struct("general", 2000, 200000, 64.0, 40.0, 4096, (), False),
     "owner": Struct("tile", 4096, 5596, 41.0, 56.0, 2048, (1024,), False),
     "runs32": Struct("tile", 2048, 2500, 410.0, 500.0, 1024, (), False),
@@ -206,7 +214,9 @@ def _tile(tw, dense, ordered, rg=1):
 CASES = (
     [Case(f"short-{d}", "short", d, {}, {"path": "short"}, "k_row (+ k_symbolic / k_numeric on spilled rows)", None)
      for d in DTYPES] +
-    [Case("short-kshort-f64", "short", "f64", {"SPG_SHORT_KERNEL": "short"}, {"path": "short"}, "k_short", None)] +
+    [Case("short-kshort-f64", "short", "f64", {"SPG_SHORT_KERNEL": "short"}, {"path": "short"}, "k_short", None),
+     Case("short64-kshort-f64", "short64", "f64", {"SPG_SHORT_KERNEL": "short"}, {"path": "short"},
+          "k_short (ALG1: the single pass holds)", None)] +
     [Case(f"general-{d}", "general", d, {}, {"path": "general"}, "k_symbolic / k_numeric", None) for d in DTYPES] +
     [Case(f"owner-sparse-{d}", "owner", d, {}, _tile(2048, False, False), "k_tile<T, DENSE=0>", "k_tile_sym8c")
      for d in ("f32", "c64")] +
@@ -372,7 +382,10 @@ Meta = namedtuple("Meta", "edge special items spill")
 def _inputs(struct, dname):
     S = STRUCTS[struct]
     rng = np.random.default_rng(seed_of("instantiations", struct, dname))
-    A, B, meta = (_short_inputs if S.kind == "short" else _wide_inputs)(S, dname, rng)
+    if S.kind == "short":
+        A, B, meta = _short_inputs(S, dname, rng, len65=struct != "short64")
+    else:
+        A, B, meta = _wide_inputs(S, dname, rng)
     for M in (A, B):
         for a in (M.data, M.indices, M.indptr):
             a.setflags(write=False)
@@ -496,7 +509,7 @@ def row_stats(A, B, i):
     return len(js), len(cols), int(np.isin(cols >> 5, flagged).sum()), len(u)
 
 
-def _short_inputs(S, dname, rng):
+def _short_inputs(S, dname, rng, len65=True):
     dt = DTYPES[dname]
     k, n = S.k, S.n
     w0, w1 = 40, 41                                   # the bitmap words of the flag rows
@@ -540,7 +553,11 @@ def _short_inputs(S, dname, rng):
         put(f"p{P}", s10(x) + s1(y)); fill(2)
     put("p641", s10(63) + [special["p11"]]); fill(2)
     for m in (1, 63, 64, 65):
-        put(f"len{m}", s1(m, 10)); fill(2)
+        if m == 65 and not len65:
+            fill(1)                                            # (short64: an ordinary row in its place)
+        else:
+            put(f"len{m}", s1(m, 10))
+        fill(2)
     put("flag64", [special[f"flag{i}"] for i in range(4)]); fill(2)
     put("flag65", [special[f"flag{i}"] for i in range(5)]); fill(2)
     put("onlyempty", [special["empty"]]); put("len0'", [])

@@ -30,7 +30,7 @@ def _crow(ref, i):
 
 def test_case_table_covers_every_kernel_and_dtype():
     have = {(c.id.rsplit("-", 1)[0] if not c.id.endswith("rg1") else "sparse8192-rg1", c.dname) for c in inst.CASES}
-    want = ([("short", d) for d in inst.DTYPES] + [("short-kshort", "f64")] + [("general", d) for d in inst.DTYPES] +
+    want = ([("short", d) for d in inst.DTYPES] + [("short-kshort", "f64"), ("short64-kshort", "f64")] + [("general", d) for d in inst.DTYPES] +
             [("owner-sparse", "f32"), ("owner-sparse", "c64"), ("owner-dense", "f32"), ("owner-dense", "c64"),
              ("runs32", "f32"), ("dense1024", "f64"), ("dense1024", "c128"), ("dense2048", "f64"),
              ("sparse4096", "f64"), ("sparse4096", "c128"), ("sparse8192", "f64"), ("sparse8192-rg1", "f64")])
@@ -167,7 +167,10 @@ def test_short_case_rows_sit_on_the_kernel_limits(case):
     s = meta.spill
     n = B.shape[1]
     assert (inst.ROW_ENTRIES, inst.ROW_PREG, inst.ROW_LCAP, 32 * inst.ROW_NW) == (64, 640, 64, 16384)
-    for m in (63, 64, 65):
+    # (short64 is `short` without the 65-entry row: its longest A row has exactly 64 entries)
+    with65 = inst.CASE[case].struct != "short64"
+    assert ("len65" in s) == with65 and np.diff(A.indptr).max() == (65 if with65 else 64)
+    for m in (63, 64, 65) if with65 else (63, 64):
         assert s[f"len{m}"][0] == m and s[f"len{m}"][4] == (m <= 64)
     for P in (128, 129, 256, 257, 384, 385, 512, 513, 640, 641):
         e, prod, L, nz, taken = s[f"p{P}"]
@@ -175,7 +178,8 @@ def test_short_case_rows_sit_on_the_kernel_limits(case):
     assert s["p640"][0] == 64 and s["p641"][0] == 64
     assert s["flag64"][2] == 64 and s["flag64"][4] and s["flag65"][2] == 65 and not s["flag65"][4]
     assert s["flag64"][1] == 64 and s["flag64"][3] == 62           # two columns hit twice
-    assert [lab for lab, v in s.items() if not v[4]] == ["p641", "len65", "flag65"]   # spilled, each for one reason
+    spilled = ["p641", "len65", "flag65"] if with65 else ["p641", "flag65"]
+    assert [lab for lab, v in s.items() if not v[4]] == spilled                       # spilled, each for one reason
     # the oracle shows the same counts; 640 distinct outputs exceed the stage window of every type
     # that has one within 640 (fp64 / complex64 517 or 602, complex128 387)
     for lab, i in meta.edge.items():

@@ -38,6 +38,22 @@ def test_short_cases_fit_the_single_pass_estimate(case):
     assert len(inst.reference(case)[1]) <= inst.alg1_estimate(A, B)
 
 
+def test_short64_holds_the_single_pass_on_k_short():
+    """short64-kshort-f64: k_short's single pass refuses only A rows of more than 64 entries (it
+    takes any product count up to 65535), and gives up past the estimate: neither happens here, so
+    ALG1 keeps the C that pass wrote."""
+    case = "short64-kshort-f64"
+    A, B, meta = inst.inputs(case)
+    assert inst.CASE[case].env == {"SPG_SHORT_KERNEL": "short"}
+    assert np.diff(A.indptr).max() == 64 and A.shape[0] == inst.ROWS
+    assert max(v[1] for v in meta.spill.values()) == 641 < 65535
+    assert len(inst.reference(case)[1]) <= inst.alg1_estimate(A, B)
+    assert inst.plan_case(case)["path"] == "short"
+    # the same rows as `short` but for the 65-entry one
+    edges = set(inst.inputs("short-kshort-f64")[2].edge)
+    assert set(meta.edge) == edges - {"len65"} and "len65" in edges
+
+
 def test_poison_schedule():
     seen = {(fill, inst.POISON_WIDTHS[(ai + fi) % 2]) for ai in range(len(inst.ALGS))
             for fi, fill in enumerate(inst.POISON_FILLS)}
