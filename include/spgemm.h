@@ -354,6 +354,68 @@ spg_status_t spg_canonicalize_nnz(spg_handle_t handle, const spg_csr_t *A, const
 spg_status_t spg_canonicalize(spg_handle_t handle, const spg_csr_t *A, const int32_t *coo_rows,
                               unsigned ops, spg_csr_t *C, size_t workspace_bytes, void *workspace);
 
+/* Sparse -> dense: D = A as a dense matrix, scipy's csr_todense (A.toarray()).  (cusparse<t>csr2dense
+ * and cusparseSparseToDense as called by cupyx.cusparse.csr2dense, csc2dense and sparseToDense,
+ * cupy-src/cupyx/cusparse.py:768-797, :800-829 and :1805-1833; cupyx's own kernel behind
+ * csr_matrix.toarray(), cupy-src/cupyx/scipy/sparse/_csr.py:383-428, which adds duplicates with
+ * atomics.  Added within 0.2.0: a caller detects it by symbol lookup.)
+ *   D is A->rows x A->cols of A's value type, SPG_ORDER_ROW or SPG_ORDER_COL, ld at least the minor
+ *   extent.  Every element of the extent is written; nothing between the minor extent and ld is
+ *   touched; D is never read.  A need not be canonical: unsorted rows and duplicates are allowed
+ *   (indices must lie in [0, cols), not checked: an entry outside is skipped).
+ *   Element (i, j) is 0 + v1 + v2 + ... over row i's entries with column j, in stored order, every
+ *   add separately rounded, complex values part by part: a lone -0.0 arrives as +0.0, and
+ *   (1e16, 1.0, -1e16) on one element gives 0.0, as in scipy.  The special-value rule is the one
+ *   above: +-0 results, denormals and +-inf bit for bit, NaN exactly where scipy has one, its sign
+ *   and payload unspecified.  Identical from run to run: no global atomic, no workspace.
+ *   A CSC matrix is the same call on its arrays read as the CSR of the transpose, with D of the
+ *   opposite order.
+ *   rows == 0 or cols == 0 succeeds without a launch; nnz == 0 writes zeros.  Both indptr types.
+ *   Stream-ordered; does not wait.  Timed under SPG_PHASE_LAYOUT (k_csr2dense).
+ *   Status: NULL handle SPG_STATUS_NOT_INITIALIZED (checked first).  SPG_STATUS_INVALID_VALUE for a
+ *   NULL A or D, a NULL array that is needed, a D that is not A's shape and value type, an order
+ *   that is neither, an ld below the minor extent. */
+spg_status_t spg_csr2dense(spg_handle_t handle, const spg_csr_t *A, spg_dense_t *D);
+
+/* Dense -> sparse: C = the nonzero elements of D as canonical CSR, scipy's csr_matrix(D), in two
+ * calls like the addition -- a structure pass that writes C's row pointer and returns nnz(C), then
+ * a value pass into the caller's C.  (cusparse<t>dense2csr with its nnz pass and
+ * cusparseDenseToSparse_analysis / _convert as called by cupyx.cusparse.dense2csr, dense2csc and
+ * denseToSparse, cupy-src/cupyx/cusparse.py:1188-1228, :1146-1185 and :1733-1802; cupyx's
+ * csr_matrix(dense), cupy-src/cupyx/scipy/sparse/_csr.py:60-80 and its kernels :1158-1210.  Added
+ * within 0.2.0: a caller detects it by symbol lookup.)
+ *   D: rows x cols of any of the four value types, either order, any ld at least the minor extent;
+ *     cols above 2^31 - 1: SPG_STATUS_NOT_SUPPORTED.  C's row pointer may be int32 or int64.
+ *   An element is kept iff its value != 0, decided on its integer bits (no float mode can flush a
+ *     denormal): +-0 is dropped; denormals, +-inf and NaN are kept; a complex value is dropped only
+ *     when both parts are +-0.  Kept values are moved bit for bit, NaN sign and payload included
+ *     (the transpose's rule).  Columns ascend inside a row: C is canonical by construction, and
+ *     equals scipy's csr_matrix(D) array for array.  A CSC result is the same pair of calls on D
+ *     read as its transpose (the opposite order).  Identical from run to run.
+ *   spg_dense2csr_nnz, workspace == NULL: size query, *workspace_bytes is set by host arithmetic
+ *     and nothing is launched.  workspace != NULL: *workspace_bytes must be >= the queried size;
+ *     writes C_indptr (rows + 1 entries of C_indptr_type) and *nnzC, waiting for the device once,
+ *     for nnzC.  SPG_STATUS_OVERFLOW when nnzC does not fit an int32 C_indptr (*nnzC is still set:
+ *     call again with an int64 array).
+ *   spg_dense2csr: takes the workspace exactly as spg_dense2csr_nnz left it, for the same D (which
+ *     must not have changed); C->indptr is the array that call wrote, C->indices / C->values hold
+ *     C->nnz = nnzC entries.  Stream-ordered; does not wait.
+ *   Neither call allocates device memory: every device scalar lives in the workspace.
+ *   Status: NULL handle SPG_STATUS_NOT_INITIALIZED (checked first).  SPG_STATUS_INVALID_VALUE for a
+ *     NULL D, workspace_bytes or nnzC; a NULL C_indptr with a workspace; an order that is neither;
+ *     an ld below the minor extent; a C_indptr_type that is neither index type; a workspace below
+ *     the queried size (spg_dense2csr: or NULL); a NULL C; a C that is not D's shape and value
+ *     type; a NULL array that is needed.
+ *   Degenerate sizes: rows == 0 and cols == 0 succeed without a kernel and leave an all-zero row
+ *     pointer; an all-zero D gives nnzC == 0.
+ *   Timing: the count and row-pointer kernels (k_dn_count, k_dn_indptr) under SPG_PHASE_SYMBOLIC,
+ *     the scan under SPG_PHASE_SCAN, the value kernel (k_dn_fill) under SPG_PHASE_NUMERIC. */
+spg_status_t spg_dense2csr_nnz(spg_handle_t handle, const spg_dense_t *D, void *C_indptr,
+                               spg_index_t C_indptr_type, int64_t *nnzC, size_t *workspace_bytes,
+                               void *workspace);
+spg_status_t spg_dense2csr(spg_handle_t handle, const spg_dense_t *D, spg_csr_t *C,
+                           size_t workspace_bytes, void *workspace);
+
 /* ALG1 single pass: after spg_symbolic, C's column indices and values may already sit
  * compact in the workspace (nnzC entries at *indices / *values; NULL otherwise).  A
  * caller may hand exactly these pointers to spg_numeric as C->indices / C->values: the
@@ -475,10 +537,12 @@ typedef enum {
     SPG_PHASE_PRODUCTS = 0,   /* k_row_products: P_i per row                      */
     SPG_PHASE_SCAN = 1,       /* k_scan_lb / k_items_to_rowptr: prefix sums       */
     SPG_PHASE_SYMBOLIC = 2,   /* k_row (count) / k_tile_sym(_seg) / k_symbolic;    */
-                              /* spg_csrgeam_nnz's k_geam_mark / k_geam_count      */
+                              /* spg_csrgeam_nnz's k_geam_mark / k_geam_count;     */
+                              /* spg_dense2csr_nnz's k_dn_count / k_dn_indptr      */
     SPG_PHASE_NUMERIC = 3,    /* k_row / k_tile_dn / k_tile_sp / k_tile /          */
                               /* k_numeric: values (ALG1 also structure); one       */
-                              /* kernel per launch; spg_csrgeam's k_geam_fill       */
+                              /* kernel per launch; spg_csrgeam's k_geam_fill;      */
+                              /* spg_dense2csr's k_dn_fill                          */
     SPG_PHASE_COMPACT = 4,    /* k_compact: ALG1 copy into C                        */
     SPG_PHASE_VALIDATE = 5,   /* k_validate                                         */
     SPG_PHASE_SPILL = 6,      /* k_symbolic / k_numeric over the rows the short-row */
@@ -487,7 +551,8 @@ typedef enum {
     SPG_PHASE_LAYOUT = 8,     /* the tile path's B re-layout: once per plan          */
                               /* (k_tile_index, k_bt_count, k_bj16, k_bt_pack) and   */
                               /* per tile group (k_bt_fill, spg_numeric_tiles);       */
-                              /* spg_csr2csc's passes (k_tr_hist, k_tr_scatter)       */
+                              /* spg_csr2csc's passes (k_tr_hist, k_tr_scatter);      */
+                              /* spg_csr2dense's k_csr2dense                          */
     SPG_NUM_PHASES = 9
 } spg_phase_t;
 

@@ -49,7 +49,8 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_set_timing", "spg_get_timing", "spg_result_in_workspace", "spg_spmv",
            "spg_spgemm_ws", "spg_plan_info", "spg_tile_value_offsets", "spg_tile_values",
            "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm", "spg_csr2csc",
-           "spg_csrgeam_nnz", "spg_csrgeam", "spg_canonicalize_nnz", "spg_canonicalize")
+           "spg_csrgeam_nnz", "spg_csrgeam", "spg_canonicalize_nnz", "spg_canonicalize",
+           "spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr")
 
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
@@ -131,6 +132,10 @@ def load():
             "spg_canonicalize_nnz": (ctypes.c_int, [vp, csrp, vp, ctypes.c_uint, vp, ctypes.c_int,
                                                     ctypes.POINTER(i64), ctypes.POINTER(sz), vp]),
             "spg_canonicalize": (ctypes.c_int, [vp, csrp, vp, ctypes.c_uint, csrp, sz, vp]),
+            "spg_csr2dense": (ctypes.c_int, [vp, csrp, dnp]),
+            "spg_dense2csr_nnz": (ctypes.c_int, [vp, dnp, vp, ctypes.c_int, ctypes.POINTER(i64),
+                                                 ctypes.POINTER(sz), vp]),
+            "spg_dense2csr": (ctypes.c_int, [vp, dnp, csrp, sz, vp]),
             "spg_symbolic": (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.POINTER(i64)]),
             "spg_numeric": (ctypes.c_int, [vp, vp, vp, csrp]),
             "spg_peak_bytes": (ctypes.c_int, [vp, ctypes.POINTER(sz)]),

@@ -27,6 +27,7 @@
 #include "spgemm_transpose.hpp"
 #include "spgemm_geam.hpp"
 #include "spgemm_canon.hpp"
+#include "spgemm_dense.hpp"
 
 using namespace spg;
 
@@ -1748,6 +1749,119 @@ spg_status_t gm_values(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, s
     return SPG_STATUS_SUCCESS;
 }
 
+// ----------------------------------------------------------------------------- spg_csr2dense / spg_dense2csr
+
+// what the three entry points ask of a dense operand (check_dense, plus a known value type and
+// columns that fit C's int32 indices)
+spg_status_t dn_check(const spg_dense_t* D) {
+    spg_status_t st = check_dense(D);
+    if (st) return st;
+    if (D->value_type != SPG_R_32F && D->value_type != SPG_R_64F && D->value_type != SPG_C_32F &&
+        D->value_type != SPG_C_64F)
+        return SPG_STATUS_NOT_SUPPORTED;
+    if (D->cols > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;
+    return SPG_STATUS_SUCCESS;
+}
+
+// 16-byte accesses need every row of a row-major D to start on a 16-byte boundary (spg_spmm's rule)
+inline bool dn_wide(const spg_dense_t& D) {
+    return D.order == SPG_ORDER_ROW &&
+           ((uintptr_t)D.values | (uintptr_t)(D.ld * (int64_t)vbytes(D.value_type))) % 16 == 0;
+}
+
+// blocks of a kernel that strides over `tasks` workgroup tasks (32-bit work-item count: spmm_grid)
+inline unsigned dn_grid(int64_t tasks) {
+    const int64_t cap = ((int64_t)1 << 31) / ((int64_t)DV_WPB * WAVE);
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(tasks, cap));
+}
+
+template <typename T, typename IP>
+spg_status_t dn_todense(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& D) {
+    const int64_t wins = grid_for(A.cols, DV_W), tiles = grid_for(A.rows, DV_R) * wins;
+    const dim3 grid(dn_grid(tiles)), block(DV_WPB * WAVE);
+    auto go = [&](auto kernel) {
+        timed_launch(h, SPG_PHASE_LAYOUT, kernel, grid, block, A.rows, A.cols, wins, tiles, (const IP*)A.indptr,
+                     (const int32_t*)A.indices, (const T*)A.values, (T*)D.values, D.ld);
+    };
+    if (D.order == SPG_ORDER_COL) go(k_csr2dense<T, IP, true, false>);
+    else if (dn_wide(D)) go(k_csr2dense<T, IP, false, true>);
+    else go(k_csr2dense<T, IP, false, false>);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// Workspace carve of spg_dense2csr_nnz / spg_dense2csr (offsets from the 256-byte aligned base).
+struct DnLayout {
+    int64_t nseg = 1;        // segments of DV_S columns per row
+    int64_t entries = 0;     // rows * nseg: the (row, segment) table
+    int64_t tasks = 0;       // wave tasks (row-major) or workgroup tasks (column-major)
+    size_t scalars = 0;      // 16 int64: [0] the scan's total, [1] its overflow flag
+    size_t status = 0;       // look-back words of the scan over the table
+    size_t table = 0;        // entries + 1 positions (8 bytes each, whatever C's row-pointer type)
+    size_t total = 0;        // bytes to ask for (256 of slack for the base alignment)
+};
+
+DnLayout dn_layout(const spg_dense_t& D) {
+    DnLayout L;
+    L.nseg = std::max<int64_t>(1, grid_for(D.cols, DV_S));
+    L.entries = D.rows * L.nseg;
+    L.tasks = D.order == SPG_ORDER_COL ? grid_for(D.rows, DV_T) * L.nseg : L.entries;
+    Carver c;
+    L.scalars = c.take(16 * sizeof(int64_t));
+    L.status = c.take(status_bytes(L.entries));
+    L.table = c.take(sizeof(int64_t) * ((size_t)L.entries + 1));
+    L.total = c.off + 256;
+    return L;
+}
+
+// f(kernel-selecting tags): E elements per lane and step, COL the order
+template <typename T, typename F>
+void dn_dispatch_read(const spg_dense_t& D, F&& f) {
+    constexpr int EV = 16 / (int)sizeof(T);
+    if (D.order == SPG_ORDER_COL) f(std::integral_constant<int, 1>{}, std::true_type{});
+    else if (EV > 1 && dn_wide(D)) f(std::integral_constant<int, EV>{}, std::false_type{});
+    else f(std::integral_constant<int, 1>{}, std::false_type{});
+}
+
+template <typename T, typename CP>
+spg_status_t dn_structure(spg_handle_t h, const spg_dense_t& D, const DnLayout& L, char* ws, CP* Cp,
+                          int64_t* nnzC) {
+    using B = typename DnBits<T>::type;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    CP* table = (CP*)(ws + L.table);
+    const bool col = D.order == SPG_ORDER_COL;
+    const dim3 grid(dn_grid(col ? L.tasks : grid_for(L.tasks, DV_WPB))), block(DV_WPB * WAVE);
+    dn_dispatch_read<T>(D, [&](auto e, auto c) {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_dn_count<T, CP, decltype(e)::value, decltype(c)::value>, grid, block,
+                     D.rows, D.cols, L.nseg, L.tasks, (const B*)D.values, D.ld, table);
+    });
+    SPG_LAUNCHED(h);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if ((st = launch_scan<CP, CP>(h, L.entries, table, table, (unsigned long long*)(ws + L.status), scal, true)))
+        return st;
+    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(D.rows + 1, 256), 1 << 20);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_dn_indptr<CP>, dim3(pgrid), dim3(256), D.rows, L.nseg, (const CP*)table, Cp);
+    SPG_LAUNCHED(h);
+    int64_t sc[2] = {0, 0};
+    if ((st = read_scalars(h, scal, 2, sc))) return st;
+    *nnzC = sc[0];
+    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+template <typename T, typename CP>
+spg_status_t dn_values(spg_handle_t h, const spg_dense_t& D, spg_csr_t& C, const DnLayout& L, char* ws) {
+    using B = typename DnBits<T>::type;
+    const bool col = D.order == SPG_ORDER_COL;
+    const dim3 grid(dn_grid(col ? L.tasks : grid_for(L.tasks, DV_WPB))), block(DV_WPB * WAVE);
+    dn_dispatch_read<T>(D, [&](auto e, auto c) {
+        timed_launch(h, SPG_PHASE_NUMERIC, k_dn_fill<T, CP, decltype(e)::value, decltype(c)::value>, grid, block,
+                     D.rows, D.cols, L.nseg, L.tasks, (const B*)D.values, D.ld, (CP*)(ws + L.table),
+                     (int32_t*)C.indices, (B*)C.values);
+    });
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
 // ----------------------------------------------------------------------------- spg_canonicalize
 
 // bits of an index below `extent`: the bits of extent - 1 (at least one)
@@ -2448,6 +2562,68 @@ spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, 
         std::memcpy(&be, beta, sizeof(T));
         return dispatch_index(A->indptr_type, C->indptr_type, [&](auto ip, auto cp) {
             return gm_values<decltype(ip), decltype(cp), T>(h, *A, *B, *C, L, ws_base(workspace), al, be);
+        });
+    });
+}
+
+spg_status_t spg_csr2dense(spg_handle_t h, const spg_csr_t* A, spg_dense_t* D) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!A || !D) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = check_csr(A);
+    if (st || (st = dn_check(D))) return st;
+    if (D->rows != A->rows || D->cols != A->cols || D->value_type != A->value_type) return SPG_STATUS_INVALID_VALUE;
+    if (A->rows == 0 || A->cols == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    return dispatch_value(A->value_type, [&](auto tag) {
+        return dispatch_index(A->indptr_type,
+                              [&](auto ip) { return dn_todense<decltype(tag), decltype(ip)>(h, *A, *D); });
+    });
+}
+
+spg_status_t spg_dense2csr_nnz(spg_handle_t h, const spg_dense_t* D, void* C_indptr, spg_index_t C_indptr_type,
+                               int64_t* nnzC, size_t* workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!D || !workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = dn_check(D);
+    if (st) return st;
+    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const DnLayout L = dn_layout(*D);
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
+    if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    if (D->rows == 0 || D->cols == 0) {   // an all-zero row pointer
+        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type) * (size_t)(D->rows + 1), h->stream));
+        *nnzC = 0;
+        return SPG_STATUS_SUCCESS;
+    }
+    return dispatch_value(D->value_type, [&](auto tag) {
+        return dispatch_index(C_indptr_type, [&](auto cp) {
+            using CP = decltype(cp);
+            return dn_structure<decltype(tag), CP>(h, *D, L, ws_base(workspace), (CP*)C_indptr, nnzC);
+        });
+    });
+}
+
+spg_status_t spg_dense2csr(spg_handle_t h, const spg_dense_t* D, spg_csr_t* C, size_t workspace_bytes,
+                           void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!D || !C || !workspace) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = dn_check(D);
+    if (st) return st;
+    if (C->rows != D->rows || C->cols != D->cols || C->value_type != D->value_type || C->nnz < 0)
+        return SPG_STATUS_INVALID_VALUE;
+    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const DnLayout L = dn_layout(*D);
+    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if (D->rows == 0 || D->cols == 0 || C->nnz == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    return dispatch_value(D->value_type, [&](auto tag) {
+        return dispatch_index(C->indptr_type, [&](auto cp) {
+            return dn_values<decltype(tag), decltype(cp)>(h, *D, *C, L, ws_base(workspace));
         });
     });
 }

@@ -59,7 +59,8 @@ def check_availability(name: str) -> bool:
     Memoized like the reference's ``@_util.memoize()`` check (cusparse.py:169-186)."""
     global _available
     if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr", "csrgeam2", "csrgeam",
-                    "canonicalize", "csrsort"):
+                    "canonicalize", "csrsort", "csr2dense", "csc2dense", "dense2csr", "dense2csc",
+                    "denseToSparse", "sparseToDense"):
         raise ValueError(f"No available version information specified for {name}")
     if _available is None:
         try:
@@ -773,6 +774,198 @@ def csrsort(x):
     x.data, x.indices, _ = _canonicalize_arrays(x.data, x.indices, x.indptr, None, x.shape, _lib.SPG_CANON_SORT,
                                                 x.indptr.dtype)
     x._canonical = None   # sorted now; canonical when it holds no duplicates
+
+
+def has_dense_convert() -> bool:
+    """True when the loaded library exports spg_csr2dense and spg_dense2csr (added within 0.2.0:
+    an older development build lacks them, and the containers then keep their torch form)."""
+    lib = _lib.load()
+    return all(hasattr(lib, n) for n in ("spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr"))
+
+
+def _handle_on(dev) -> _lib.Handle:
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _lib.get_handle(idx)
+    h.set_stream(_current_stream_ptr(idx))
+    return h
+
+
+def _new_dense(m: int, n: int, dtype, dev, order: str) -> torch.Tensor:
+    if order not in ("C", "F"):
+        raise ValueError("order must be 'C' or 'F'")
+    return torch.empty((m, n), dtype=dtype, device=dev) if order == "C" \
+        else torch.empty((n, m), dtype=dtype, device=dev).t()
+
+
+def _check_out(out, m: int, n: int, dtype, dev) -> torch.Tensor:
+    if not isinstance(out, torch.Tensor):
+        raise TypeError("out must be a torch tensor")
+    if out.ndim != 2 or tuple(out.shape) != (m, n):
+        raise ValueError("out must have the matrix's shape")
+    if out.dtype != dtype or out.device != dev:
+        raise TypeError("out must be a tensor of the matrix's type on its device")
+    if _dense_layout(out) is None:
+        raise ValueError("out must have unit stride along its rows or its columns")
+    return out
+
+
+def _todense_into(data, indices, indptr, rows: int, cols: int, view: torch.Tensor) -> None:
+    """spg_csr2dense of the rows x cols CSR arrays into `view` (rows x cols, a layout
+    _dense_layout accepts); every element of the extent is written, no padding touched."""
+    if rows == 0 or cols == 0:
+        return
+    nnz = int(data.numel())
+    h = _handle_on(data.device)
+    ipd = indptr.dtype if indptr.dtype in _IT else torch.int64
+    if ipd == torch.int32 and nnz > 2 ** 31 - 1:
+        ipd = torch.int64
+    indptr, indices, data = indptr.to(ipd).contiguous(), indices.to(torch.int32).contiguous(), data.contiguous()
+    va = SpgCsr(rows, cols, nnz, indptr.data_ptr(), indices.data_ptr() if nnz else 0,
+                data.data_ptr() if nnz else 0, _IT[ipd], _VT[data.dtype])
+    vd = _dense_view(view, *_dense_layout(view))
+    check(h.lib.spg_csr2dense(h.ptr, ctypes.byref(va), ctypes.byref(vd)), "spg_csr2dense")
+
+
+def _compressed2dense(x, kind, name: str, out, order: str) -> torch.Tensor:
+    if not check_availability(name):
+        raise RuntimeError(f"{name} is not available.")
+    if not isinstance(x, kind):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError(f"{name} needs device-resident operands")
+    m, n = x.shape
+    out = _new_dense(m, n, x.data.dtype, x.device, order) if out is None else \
+        _check_out(out, m, n, x.data.dtype, x.device)
+    if kind is csr_matrix:
+        _todense_into(x.data, x.indices, x.indptr, m, n, out)
+    else:   # the CSC arrays are the CSR of the transpose: the same kernel on the swapped view
+        _todense_into(x.data, x.indices, x.indptr, n, m, out.t())
+    return out
+
+
+def csr2dense(x, out=None, order="C"):
+    """The CSR matrix ``x`` as a dense 2-D tensor on its device -- the drop-in for
+    ``cupyx.cusparse.csr2dense`` (modify_src/cupy-src/cupyx/cusparse.py:768-797), on
+    ``spg_csr2dense``.  ``x`` need not be canonical: every element is 0 + v1 + v2 + ... over its
+    stored entries in stored order, so the result equals scipy's ``toarray()`` bit for bit and is
+    the same from run to run.  ``out`` may be any row- or column-major view with a leading
+    dimension (only the extent is written); without it the result is ``order`` 'C' or 'F'."""
+    return _compressed2dense(x, csr_matrix, "csr2dense", out, order)
+
+
+def csc2dense(x, out=None, order="C"):
+    """The CSC matrix ``x`` as a dense 2-D tensor -- the drop-in for ``cupyx.cusparse.csc2dense``
+    (modify_src/cupy-src/cupyx/cusparse.py:800-829): ``spg_csr2dense`` on the CSC arrays read as
+    the CSR of the transpose, into the transposed view of the result; no transpose is made."""
+    from .sparse import csc_matrix
+    return _compressed2dense(x, csc_matrix, "csc2dense", out, order)
+
+
+def sparseToDense(x, out=None):
+    """A csr_matrix, csc_matrix or coo_matrix as a dense 2-D tensor -- the drop-in for
+    ``cupyx.cusparse.sparseToDense`` (modify_src/cupy-src/cupyx/cusparse.py:1805-1833).  COO
+    entries are grouped by row first, stably (spg_canonicalize with no op), so duplicates are
+    still added in stored order."""
+    from .sparse import coo_matrix, csc_matrix
+    if not check_availability("sparseToDense"):
+        raise RuntimeError("sparseToDense is not available.")
+    if isinstance(x, csr_matrix):
+        return csr2dense(x, out=out)
+    if isinstance(x, csc_matrix):
+        return csc2dense(x, out=out)
+    if not isinstance(x, coo_matrix):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError("sparseToDense needs device-resident operands")
+    m, n = x.shape
+    out = _new_dense(m, n, x.data.dtype, x.device, "C") if out is None else \
+        _check_out(out, m, n, x.data.dtype, x.device)
+    _todense_into(*_canonicalize_arrays(x.data, x.col, None, x.row, x.shape, 0), m, n, out)
+    return out
+
+
+def _dense2csr_arrays(t: torch.Tensor):
+    """(data, indices, indptr) of the canonical CSR form of the 2-D device tensor ``t`` (any
+    strides), on spg_dense2csr_nnz + spg_dense2csr.  int32 indptr unless nnz needs int64."""
+    dev, dt = t.device, t.dtype
+    m, n = int(t.shape[0]), int(t.shape[1])
+    lay = _dense_layout(t)
+    if lay is None:
+        t = t.contiguous()
+        lay = _dense_layout(t)
+    h = _handle_on(dev)
+    vd = _dense_view(t, *lay)
+    ws_bytes = ctypes.c_size_t(0)
+    nnz = ctypes.c_int64(0)
+    check(h.lib.spg_dense2csr_nnz(h.ptr, ctypes.byref(vd), None, _lib.SPG_INDEX_32I, ctypes.byref(nnz),
+                                  ctypes.byref(ws_bytes), None), "spg_dense2csr_nnz")
+    # workspace from torch's caching allocator on the current stream, as in _spgemm
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    ipd = torch.int32
+    c_indptr = torch.empty(m + 1, dtype=ipd, device=dev)
+    st = h.lib.spg_dense2csr_nnz(h.ptr, ctypes.byref(vd), ctypes.c_void_p(c_indptr.data_ptr()), _IT[ipd],
+                                 ctypes.byref(nnz), ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()))
+    if st == _lib.STATUS_OVERFLOW:   # nnz >= 2**31: once more with int64 row pointers
+        ipd = torch.int64
+        c_indptr = torch.empty(m + 1, dtype=ipd, device=dev)
+        st = h.lib.spg_dense2csr_nnz(h.ptr, ctypes.byref(vd), ctypes.c_void_p(c_indptr.data_ptr()), _IT[ipd],
+                                     ctypes.byref(nnz), ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()))
+    check(st, "spg_dense2csr_nnz")
+    nc = int(nnz.value)
+    c_indices = torch.empty(nc, dtype=torch.int32, device=dev)
+    c_data = torch.empty(nc, dtype=dt, device=dev)
+    vc = SpgCsr(m, n, nc, c_indptr.data_ptr(), c_indices.data_ptr() if nc else 0, c_data.data_ptr() if nc else 0,
+                _IT[ipd], _VT[dt])
+    check(h.lib.spg_dense2csr(h.ptr, ctypes.byref(vd), ctypes.byref(vc), ws_bytes, ctypes.c_void_p(ws.data_ptr())),
+          "spg_dense2csr")
+    return c_data, c_indices, c_indptr
+
+
+def _check_dense_operand(x, name: str) -> torch.Tensor:
+    if not check_availability(name):
+        raise RuntimeError(f"{name} is not available.")
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.ndim != 2:
+        raise ValueError("expected a 2-D tensor")
+    if x.dtype not in _VT:
+        raise TypeError(f"{name} supports float32/float64/complex64/complex128, got {x.dtype}")
+    if x.device.type != "cuda":
+        raise RuntimeError(f"{name} needs device-resident operands")
+    return x
+
+
+def dense2csr(x):
+    """The 2-D device tensor ``x`` as a canonical csr_matrix -- the drop-in for
+    ``cupyx.cusparse.dense2csr`` (modify_src/cupy-src/cupyx/cusparse.py:1188-1228), on
+    ``spg_dense2csr_nnz`` + ``spg_dense2csr``.  An element is kept iff it is != 0 (+-0 dropped;
+    denormals, +-inf and NaN kept) and moved bit for bit: scipy's ``csr_matrix(x)`` array for
+    array.  Row-major and column-major strides are read as they are, anything else is copied."""
+    x = _check_dense_operand(x, "dense2csr")
+    return csr_matrix._from_parts(*_dense2csr_arrays(x), x.shape, canonical=True)
+
+
+def dense2csc(x):
+    """The 2-D device tensor ``x`` as a canonical csc_matrix -- the drop-in for
+    ``cupyx.cusparse.dense2csc`` (modify_src/cupy-src/cupyx/cusparse.py:1146-1185): the CSR
+    conversion of the transposed view, which moves no data."""
+    from .sparse import csc_matrix
+    x = _check_dense_operand(x, "dense2csc")
+    return csc_matrix(_dense2csr_arrays(x.t()), shape=x.shape, canonical=True)
+
+
+def denseToSparse(x, format="csr"):
+    """``x`` as a csr_matrix, csc_matrix or coo_matrix -- the drop-in for
+    ``cupyx.cusparse.denseToSparse`` (modify_src/cupy-src/cupyx/cusparse.py:1733-1802)."""
+    from .sparse import coo_matrix
+    if format == "csr":
+        return dense2csr(x)
+    if format == "csc":
+        return dense2csc(x)
+    if format != "coo":
+        raise TypeError("unsupported format (actual: {})".format(format))
+    c = dense2csr(_check_dense_operand(x, "denseToSparse"))
+    return coo_matrix((c.data, (c._row_ids(), c.indices.to(torch.int64))), shape=c.shape)
 
 
 def num_products(a: csr_matrix, b: csr_matrix) -> int:

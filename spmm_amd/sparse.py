@@ -89,6 +89,91 @@ def _engine_canonicalizes(t: torch.Tensor, shape) -> bool:
     return cusparse.has_canonicalize()
 
 
+def _engine_converts_dense(t: torch.Tensor) -> bool:
+    """Dense <-> CSR of these tensors runs on spg_csr2dense / spg_dense2csr: they sit on a GPU
+    and the loaded library exports the symbols (otherwise the torch form of the same rules serves)."""
+    if t.device.type != "cuda":
+        return False
+    from . import cusparse
+    return cusparse.has_dense_convert()
+
+
+_VALUE_TYPES = (torch.float32, torch.float64, torch.complex64, torch.complex128)
+
+
+def _dense_operand(x, dtype, device) -> torch.Tensor:
+    """The 2-D tensor a container is built from: a torch tensor or a numpy array, cast to
+    ``dtype`` when given and moved to ``device`` (a numpy array: the default device)."""
+    if x.ndim != 2:
+        raise ValueError("expected a 2-D array")
+    if isinstance(x, np.ndarray):
+        t = torch.from_numpy(x if x.flags.writeable else x.copy())   # (F-ordered arrays keep their strides)
+        device = device or _default_device()
+    else:
+        t = x
+        device = device or x.device
+    if dtype is not None:
+        t = t.to(_TORCH_OF[np.dtype(dtype)])
+    if t.dtype not in _VALUE_TYPES:
+        raise TypeError(f"unsupported dtype {t.dtype}")
+    return t.to(device)
+
+
+def _dense_to_csr(t: torch.Tensor):
+    """(data, indices, indptr) of scipy's csr_matrix(t) for a 2-D tensor: spg_dense2csr's rule
+    (include/spgemm.h) -- an element is kept iff its bits without the sign(s) are nonzero, kept
+    values are copied, columns ascend.  The engine for device tensors, torch ops otherwise."""
+    if _engine_converts_dense(t):
+        from . import cusparse
+        return cusparse._dense2csr_arrays(t)
+    m = int(t.shape[0])
+    parts = torch.view_as_real(t) if t.is_complex() else t
+    bits = parts.contiguous().view(torch.int32 if parts.dtype == torch.float32 else torch.int64)
+    keep = (bits & (0x7FFFFFFF if parts.dtype == torch.float32 else 0x7FFFFFFFFFFFFFFF)) != 0
+    if t.is_complex():
+        keep = keep.any(dim=-1)
+    nz = keep.nonzero()   # row-major: rows ascend, columns ascend inside a row
+    rows, cols = nz[:, 0], nz[:, 1]
+    ipd = torch.int32 if rows.numel() <= INT32_MAX else torch.int64
+    return t[rows, cols].contiguous(), cols.to(torch.int32), _indptr_from_rows(rows, m, ipd)
+
+
+def _compressed_to_dense(data, indices, indptr, n_major: int, n_minor: int) -> torch.Tensor:
+    """The n_major x n_minor row-major dense form of compressed arrays as torch ops --
+    spg_csr2dense's rule (include/spgemm.h): every element is 0 + v1 + v2 + ... over its stored
+    entries in stored order, each add rounded on its own, complex values part by part."""
+    parts = torch.view_as_real(data) if data.is_complex() else data
+    flat = torch.zeros((n_major * n_minor,) + tuple(parts.shape[1:]), dtype=parts.dtype, device=data.device)
+    if data.numel():
+        counts = (indptr[1:] - indptr[:-1]).to(torch.int64)
+        major = torch.repeat_interleave(torch.arange(n_major, device=data.device), counts)
+        key_s, order = torch.sort(major * max(n_minor, 1) + indices.to(torch.int64), stable=True)
+        uniq, runs = torch.unique_consecutive(key_s, return_counts=True)
+        vals = parts[order].clone()
+        starts = torch.zeros(runs.numel(), dtype=torch.int64, device=data.device)
+        starts[1:] = torch.cumsum(runs, 0)[:-1]
+        vals[starts] = torch.zeros_like(vals[starts]) + vals[starts]   # the sum starts from +0
+        flat[uniq] = _segmented_sequential_sum(vals, runs)
+    flat = flat.reshape((n_major, n_minor) + tuple(parts.shape[1:]))
+    return torch.view_as_complex(flat) if data.is_complex() else flat
+
+
+def _ordered(dense: torch.Tensor, order, out):
+    """A row-major result in the asked order ('C', 'F' or None), or copied into ``out``."""
+    if order not in (None, "C", "F"):
+        raise ValueError("order must be 'C' or 'F'")
+    if out is not None:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch tensor")
+        if tuple(out.shape) != tuple(dense.shape):
+            raise ValueError("out must have the matrix's shape")
+        if out.dtype != dense.dtype or out.device != dense.device:
+            raise TypeError("out must be a tensor of the matrix's type on its device")
+        out.copy_(dense)
+        return out
+    return dense.t().contiguous().t() if order == "F" else dense.contiguous()
+
+
 def _negated(x: torch.Tensor) -> torch.Tensor:
     """-x as a flip of every sign bit (torch's complex negative is 0 - x on some paths, which
     leaves a +0.0 part at +0.0)."""
@@ -184,6 +269,14 @@ class _SparseBase:
     def toarray(self) -> np.ndarray:
         return self.get().toarray()
 
+    def todense(self, order=None, out=None) -> torch.Tensor:
+        """The matrix as a dense 2-D tensor on its device (cupyx _csr.py:383-428, _csc.py and
+        _coo.py todense): every element is 0 + v1 + v2 + ... over its stored entries in stored
+        order, scipy's ``toarray()`` bit for bit.  ``order`` 'C' (the default) or 'F'; ``out`` any
+        row- or column-major view of the matrix's shape, type and device.  spg_csr2dense for
+        device tensors, else the torch form of the same rule."""
+        raise NotImplementedError
+
     def __matmul__(self, other):
         return self.tocsr().__matmul__(other)
 
@@ -206,7 +299,7 @@ class _Compressed(_SparseBase):
             alpha = -1 if lhs_negative else 1
             beta = -1 if rhs_negative else 1
             return self._add_sparse(other, alpha, beta)
-        # (a dense operand: the reference adds self.todense(); there is no device todense here)
+        # (a dense operand: the reference adds self.todense(); dense results are not produced here)
         return NotImplemented
 
     def __add__(self, other):
@@ -280,6 +373,11 @@ class csr_matrix(_Compressed):
             self.indptr = _as_tensor(S.indptr, ipd, device)
             self._shape = tuple(int(s) for s in S.shape)
             self._canonical = canon
+        elif isinstance(arg1, (torch.Tensor, np.ndarray)):   # a dense matrix (cupyx _csr.py:60-80)
+            t = _dense_operand(arg1, dtype, device)
+            self.data, self.indices, self.indptr = _dense_to_csr(t)
+            self._shape = (int(t.shape[0]), int(t.shape[1]))
+            self._canonical = True
         else:
             raise TypeError(f"unsupported csr_matrix argument {type(arg1)}")
         if self.data.dtype not in (torch.float32, torch.float64, torch.complex64, torch.complex128):
@@ -382,6 +480,14 @@ class csr_matrix(_Compressed):
 
     def tocsr(self, copy=False):
         return self.copy() if copy else self
+
+    def todense(self, order=None, out=None) -> torch.Tensor:
+        if _engine_converts_dense(self.data):
+            from . import cusparse
+            if order not in (None, "C", "F"):
+                raise ValueError("order must be 'C' or 'F'")
+            return cusparse.csr2dense(self, out=out, order=order or "C")
+        return _ordered(_compressed_to_dense(self.data, self.indices, self.indptr, *self._shape), order, out)
 
     def get(self):
         """Copy to the host as a scipy.sparse.csr_matrix (cupy's .get())."""
@@ -553,6 +659,19 @@ class coo_matrix(_SparseBase):
         keep = self.data != 0
         self.data, self.row, self.col = self.data[keep].contiguous(), self.row[keep], self.col[keep]
 
+    def todense(self, order=None, out=None) -> torch.Tensor:
+        if _engine_converts_dense(self.data) and max(self._shape) <= INT32_MAX:
+            from . import cusparse
+            d = cusparse.sparseToDense(self, out=out)
+            return d if out is not None else _ordered(d, order, None)
+        # grouped by row, stably, duplicates kept: the per-element order is the stored one
+        key = self.row * max(self._shape[1], 1) + self.col
+        _, perm = torch.sort(key, stable=True)
+        rows = self.row[perm]
+        ipd = torch.int32 if rows.numel() <= INT32_MAX else torch.int64
+        return _ordered(_compressed_to_dense(self.data[perm], self.col[perm], _indptr_from_rows(
+            rows, self._shape[0], ipd), *self._shape), order, out)
+
     def get(self):
         import scipy.sparse as sp
         return sp.coo_matrix((self.data.cpu().numpy(), (self.row.cpu().numpy(), self.col.cpu().numpy())),
@@ -598,6 +717,14 @@ class csc_matrix(_Compressed):
             if self.indptr.numel() != self._shape[1] + 1:
                 raise ValueError("indptr length must be columns + 1")
             return
+        if isinstance(arg1, (torch.Tensor, np.ndarray)):   # a dense matrix: the CSR form of its transposed view
+            t = _dense_operand(arg1, None, torch.device(device) if device is not None else None)
+            self.data, self.indices, self.indptr = _dense_to_csr(t.t())
+            self._shape = (int(t.shape[0]), int(t.shape[1]))
+            self._canonical = True
+            return
+        if not hasattr(arg1, "tocsc"):
+            raise TypeError(f"unsupported csc_matrix argument {type(arg1)}")
         S = arg1.tocsc()
         device = device or _default_device()
         self.data = _as_tensor(S.data, _TORCH_OF[np.dtype(S.dtype)], device)
@@ -652,6 +779,15 @@ class csc_matrix(_Compressed):
         cols = torch.repeat_interleave(torch.arange(n, device=self.device), counts)
         return coo_matrix((self.data, (self.indices.to(torch.int64), cols)), shape=(m, n),
                           device=self.device).tocsr()
+
+    def todense(self, order=None, out=None) -> torch.Tensor:
+        m, n = self._shape
+        if _engine_converts_dense(self.data):
+            from . import cusparse
+            if order not in (None, "C", "F"):
+                raise ValueError("order must be 'C' or 'F'")
+            return cusparse.csc2dense(self, out=out, order=order or "C")
+        return _ordered(_compressed_to_dense(self.data, self.indices, self.indptr, n, m).t(), order, out)
 
     def get(self):
         import scipy.sparse as sp
