@@ -11,6 +11,9 @@
 //                                products per wave instruction, 8 instructions in flight; with
 //                                `store` also a non-temporal 12-byte-per-2-products output stream
 //                                (C's columns and values)
+//   segs    PLACE [waves_per_cu] the dense-tile kernel's gather in its real form: 10-byte records,
+//                                a segment table, segments back to back (PLACE 0) or placed so
+//                                that none straddles a 128-byte line it need not (PLACE 1)
 //
 // Prints one JSON line per run: useful bytes (12 per product, + the stream), kernel ms, GB/s.
 // Under `rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum
@@ -23,6 +26,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+
+#include "../spmm_amd/csrc/seg_place.hpp"   // the engine's placement rule (segs)
 
 #define CK(x)                                                                        \
     do {                                                                             \
@@ -104,9 +109,143 @@ __global__ __launch_bounds__(WPB * 64) void k_gather(const uint32_t* __restrict_
     if (acc == 123.456) sink[0] = acc;
 }
 
+// ---- segs: the dense-tile kernel's record gather with its real record form and a segment table.
+// 10-byte fp64 records read as load_rec_at reads them (one 12-byte load from the dword at or
+// below the record), 65536 segments per slice (a 2048-column tile of config 4's B: one segment
+// per B row, 10.25 records on average), every segment found through an 8-byte {byte offset,
+// record count} table entry.  The lengths repeat in a pattern of 16 (164 records, rotated from
+// one group of 16 to the next) so that product t of a wave finds its segment and its place in it
+// from a small LDS map instead of a scan: group t / 164 is 16 A entries, entry j of it is segment
+// j of a random group of 16 segments of the slice, another group for every entry.
+constexpr int PSEG = 16, PSUM = 164;
+constexpr uint32_t LINE = spg::SEG_LINE;
+static const int h_plen[PSEG] = {10, 5, 14, 9, 13, 10, 16, 6, 11, 10, 7, 13, 9, 12, 8, 11};   // 12 of 16 <= 12
+
+template <int U>
+__global__ __launch_bounds__(WPB * 64) void k_gather_segs(const char* __restrict__ rec, int64_t slice_bytes,
+                                                          const uint2* __restrict__ tab, int nseg,
+                                                          const uint16_t* __restrict__ gmap, int chunks,
+                                                          double* sink) {
+    __shared__ uint16_t map[PSEG * PSUM];   // [rotation][product of the group] -> entry << 8 | record
+    for (int i = threadIdx.x; i < PSEG * PSUM; i += WPB * 64) map[i] = gmap[i];
+    __syncthreads();
+    const int l = threadIdx.x & 63;
+    const uint32_t wave = blockIdx.x * WPB + (threadIdx.x >> 6);
+    const char* rb = rec + (int64_t)(blockIdx.x & 7) * slice_bytes;
+    const uint2* tp = tab + (int64_t)(blockIdx.x & 7) * nseg;
+    const uint32_t ngrp = (uint32_t)nseg / PSEG;
+    double acc = 0.0;
+    int cacc = 0;
+    for (int c0 = 0; c0 < chunks; c0 += U) {
+        uint32_t off[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t t = (uint32_t)(c0 + u) * 64u + (uint32_t)l;
+            const uint32_t grp = t / (uint32_t)PSUM, r = t - grp * (uint32_t)PSUM;
+            const uint32_t rot = grp & (PSEG - 1);   // the length pattern's rotation for these 16 entries
+            const uint32_t m = map[rot * PSUM + r], j = m >> 8;
+            // entry j: segment j of a random group of that rotation, its own group for every entry
+            const uint32_t q = mix((grp * PSEG + j) * 2654435761u ^ wave * 40503u) % (ngrp / PSEG) * PSEG + rot;
+            const uint2 se = tp[q * PSEG + j];
+            off[u] = se.x + (m & 255u) * 10u;
+        }
+        double v[U];
+        int col[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {   // load_rec_at's fp64 form
+            const uint32_t sh = (off[u] & 2u) * 8u;
+            const uint3 x = *reinterpret_cast<const uint3*>(rb + (off[u] & ~3u));
+            const uint32_t lo = __builtin_amdgcn_alignbit(x.y, x.x, sh);
+            const uint32_t hi = __builtin_amdgcn_alignbit(x.z, x.y, sh);
+            v[u] = __hiloint2double((int)hi, (int)lo);
+            col[u] = (int)((x.z >> sh) & 0xffffu);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            acc += v[u];
+            cacc ^= col[u];
+        }
+    }
+    if (acc == 123.456 && cacc == 77) sink[0] = acc;
+}
+
+// segs PLACE [waves_per_cu]: PLACE 0 = segments back to back (today's layout: any even offset),
+// 1 = every segment placed by spg::seg_place (spmm_amd/csrc/seg_place.hpp).
+static int run_segs(int argc, char** argv, double* sink, hipEvent_t a, hipEvent_t b) {
+    const int place = std::atoi(argv[2]);
+    const int wpc = argc > 3 ? std::atoi(argv[3]) : 8;
+    constexpr int U = 8;
+    const int nseg = 65536;
+    std::vector<uint16_t> map((size_t)PSEG * PSUM);
+    for (int rot = 0; rot < PSEG; ++rot) {
+        int r = 0;
+        for (int j = 0; j < PSEG; ++j)
+            for (int kk = 0; kk < h_plen[(j + rot) % PSEG]; ++kk) map[(size_t)rot * PSUM + r++] = (uint16_t)(j << 8 | kk);
+    }
+    // one slice's table (all 8 slices are laid out alike) and its line statistics
+    std::vector<uint2> tab1((size_t)nseg);
+    uint32_t x = 0;
+    uint64_t lines = 0, nrec = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const uint32_t n = (uint32_t)h_plen[(s % PSEG + s / PSEG) % PSEG], L = n * 10u;
+        if (place) x = spg::seg_place(x, L);
+        tab1[(size_t)s] = make_uint2(x, n);
+        lines += (x + L - 1) / LINE - x / LINE + 1;
+        x += L;
+        nrec += n;
+    }
+    const int64_t slice_bytes = (int64_t)((x + 2 + LINE - 1) / LINE * LINE);   // + 2: the last load's overlap
+    std::vector<char> h((size_t)slice_bytes * 8, 0);
+    std::vector<uint2> tab((size_t)nseg * 8);
+    for (int sl = 0; sl < 8; ++sl)
+        for (int s = 0; s < nseg; ++s) {
+            tab[(size_t)sl * nseg + s] = tab1[(size_t)s];
+            for (uint32_t i = 0; i < tab1[(size_t)s].y; ++i) {
+                char* p = h.data() + (size_t)sl * slice_bytes + tab1[(size_t)s].x + i * 10u;
+                const double v = 1.0 + (double)((s + i) % 1000) * 1e-3;
+                const uint16_t c = (uint16_t)((s * 7 + i) & 2047);
+                std::memcpy(p, &v, 8);
+                std::memcpy(p + 8, &c, 2);
+            }
+        }
+    char* rec;
+    uint2* dtab;
+    uint16_t* dmap;
+    CK(hipMalloc(&rec, h.size() + 256));
+    CK(hipMemset(rec, 0, h.size() + 256));
+    CK(hipMemcpy(rec, h.data(), h.size(), hipMemcpyHostToDevice));
+    CK(hipMalloc(&dtab, tab.size() * sizeof(uint2)));
+    CK(hipMemcpy(dtab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    CK(hipMalloc(&dmap, map.size() * 2));
+    CK(hipMemcpy(dmap, map.data(), map.size() * 2, hipMemcpyHostToDevice));
+    const int64_t total_chunks = (int64_t)256 * 32 * 4096;   // 2^31 products, as `gather`
+    const int chunks = (int)(total_chunks / (256 * wpc));
+    const int blocks = 256 * wpc / WPB;
+    float best = 1e30f;
+    const int reps = 5;
+    for (int r = 0; r < reps; ++r) {
+        CK(hipEventRecord(a));
+        hipLaunchKernelGGL(k_gather_segs<U>, dim3(blocks), dim3(WPB * 64), 0, 0, rec, slice_bytes, dtab, nseg, dmap,
+                           chunks, sink);
+        CK(hipEventRecord(b));
+        CK(hipEventSynchronize(b));
+        CK(hipGetLastError());
+        float ms;
+        CK(hipEventElapsedTime(&ms, a, b));
+        if (ms < best) best = ms;
+    }
+    const double products = (double)blocks * WPB * chunks * 64;
+    std::printf("{\"mode\": \"segs\", \"place\": %d, \"slice_MB\": %.3f, \"segments\": %d, \"records\": %llu, "
+                "\"lines_per_segment\": %.4f, \"waves_per_cu\": %d, \"U\": %d, \"launches\": %d, \"products\": %.0f, "
+                "\"segments_walked\": %.0f, \"record_bytes_per_launch\": %.0f, \"best_ms\": %.4f, \"record_GBps\": %.1f}\n",
+                place, slice_bytes / 1048576.0, nseg, (unsigned long long)nrec, (double)lines / nseg, wpc, U, reps,
+                products, products / PSUM * PSEG, 10.0 * products, best, 10.0 * products / (best * 1e-3) / 1e9);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: gather_probe stream S_MB | gather S_MB L [store] [waves_per_cu] [U] [rec_bytes]\n");
+        std::fprintf(stderr, "usage: gather_probe stream S_MB | gather S_MB L [store] [waves_per_cu] [U] [rec_bytes] | segs PLACE [waves_per_cu]\n");
         return 1;
     }
     const bool stream = std::strcmp(argv[1], "stream") == 0;
@@ -116,6 +255,7 @@ int main(int argc, char** argv) {
     hipEvent_t a, b;
     CK(hipEventCreate(&a));
     CK(hipEventCreate(&b));
+    if (std::strcmp(argv[1], "segs") == 0) return run_segs(argc, argv, sink, a, b);
     if (stream) {
         const int64_t bytes = (int64_t)(smb * 1048576.0) / 16 * 16;
         uint4* p;

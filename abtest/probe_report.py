@@ -44,6 +44,12 @@ def main():
             "l2_hit_rate": round(hit / (hit + miss), 4) if hit + miss else None,
             "write_GB": round(c.get("WRITE_SIZE", 0.0) * 1024 / 1e9, 3),
             "store_GB": round(line.get("store_bytes_per_launch", 0) / 1e9, 3)})
+        if "segments_walked" in line:   # `segs`: the vector L1's read requests, per segment walked
+            tcp, lat = c.get("TCP_TCC_READ_REQ_sum"), c.get("TCP_TCC_READ_REQ_LATENCY_sum")
+            rows[-1].update({
+                "place": line["place"], "slice_MB": line["slice_MB"], "lines_per_segment": line["lines_per_segment"],
+                "tcp_read_req": tcp, "tcp_read_req_per_segment": round(tcp / line["segments_walked"], 3) if tcp else None,
+                "tcp_read_latency_per_req": round(lat / tcp, 1) if tcp and lat else None})
     for r in rows:
         print(json.dumps(r))
 

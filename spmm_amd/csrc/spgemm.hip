@@ -120,6 +120,12 @@ struct spg_plan_s {
     uint2* tidx = nullptr;          // B column-tile index, B.rows * G (start, end) pairs (a
                                     // temporary in the bitmap region, read before the symbolic pass)
     int32_t* tptr = nullptr;        // tile-major B: segment table, G * (B.rows + 1)
+    bool packed = false;            // segment pairs: the numeric kernel is k_tile_dn (packed_segments)
+    bool placed = false;            // ... and the segments are placed by seg_place (short segments)
+    uint2* pseg = nullptr;          // ... {byte offset, record count} of every (tile, B row), G * B.rows
+    int32_t* segblk = nullptr;      // ... placed: first 128-byte line of every block of SEG_BLK B rows of a
+                                    // tile, then the line behind the records; the last word (seg_end): the
+                                    // end of B's records in bytes (the sentinels' place), placed or not
     uint32_t* sidx = nullptr;       // symbolic-tile starts inside each B row, B.rows * (Gs + 1)
     void* brec = nullptr;           // tile-major B: (column, value) records (numeric tile pass)
     uint16_t* bj16 = nullptr;       // B's columns modulo 65536 (symbolic tile pass)
@@ -256,10 +262,13 @@ inline bool want_tile(const spg_csr_t& A, const spg_csr_t& B, int& tws, int& G, 
     if (frac * (double)(1 << tws) < 64.0) return false;
     // the tile-major B's segment table is int32 and its records are addressed with 32-bit
     // byte offsets
-    if (B.nnz > 2147483647LL ||
-        (double)(B.nnz + SENT_REGIONS * SENT_N) * (double)brec_bytes(B.value_type) >= 4294967296.0)
-        return false;
+    // (dense tiles may place their segments, seg_place.hpp: the bound of the placed size counts)
     G = (int)((B.cols + (1 << tws) - 1) >> tws);
+    const bool dense = (1 << tws) <= ((B.value_type == SPG_R_64F && lean) ? DN_TW_MAX : TILE_CAP);
+    const double pad = dense ? (double)(seg_bound((uint64_t)B.nnz, (uint64_t)B.rows * (uint64_t)G, 0) + 2 * SEG_LINE) : 0.0;
+    if (B.nnz > 2147483647LL ||
+        (double)(B.nnz + SENT_REGIONS * SENT_N) * (double)brec_bytes(B.value_type) + pad >= 4294967296.0)
+        return false;
     return (double)A.rows * G < 2.0e9;
 }
 
@@ -601,6 +610,7 @@ spg_status_t read_scalars(spg_handle_t h, const int64_t* dev, int n, int64_t* ou
 struct Layout {
     size_t scalars = 0, row_cnt = 0, seg = 0, spill = 0, status = 0, ub = 0, tj = 0, tx = 0;
     size_t tptr = 0, sidx = 0, items = 0, bitmap = 0, brec = 0, bj16 = 0, ext = 0, total = 0;
+    size_t pseg = 0, segblk = 0;
 };
 
 // Tile path row chunks: ALG3's chunks (items and bitmaps are sized by the largest one and
@@ -659,6 +669,41 @@ inline bool fp32_runs(const spg_plan_s& p) {
     const double seg = (double)p.B.nnz / (double)p.B.rows * (double)(1 << p.tws) / (double)p.B.cols;
     return seg >= F32_RUN_MIN;
 }
+// Plans whose numeric kernel is k_tile_dn (dense tiles under the ordered LDS add, or fp32 entry
+// runs) find B's segments through 8-byte pairs (spgemm_tile.hpp, "Segment pairs"): decided once
+// per plan (p.packed), since the workspace and the kernel follow from it.
+inline bool packed_segments(const spg_plan_s& p) {
+    if (!tile_dense(p)) return false;
+    if (p.A.value_type == SPG_R_32F) return fp32_runs(p);
+    return p.lean && (p.A.value_type == SPG_R_64F || p.A.value_type == SPG_C_64F);
+}
+// ... and place them (seg_place) where a tile's expected B segment is at most SEG_PLACE_MAX bytes
+// (config 4: 102 bytes).  Longer segments take several lines wherever they start: config3_fp32's
+// 614-byte segments lost 0.12 ms of b_layout to the placement passes and gained nothing.
+// And only where the product is large enough to pay for the placement passes: they cost a fixed
+// 0.12-0.18 ms of b_layout (one lane walks 64 segments; measured 0.17 -> 0.29 ms per product at
+// 4096 x 4596, 0.27 -> 0.45 ms on config 4) and save about 0.1 ms of the numeric pass per 1e9
+// products (config 4: 0.74 ms on 7.05e9), so they break even near 1.7e9 expected products
+// (nnz(A) x B's mean row, known without the device); the threshold leaves a factor of two.
+// SPG_SEG_PLACE=1 / 0 (read per plan: a schedule-only switch for A/B timing and the tests; results
+// are identical) places the segments of every such plan / of none.
+constexpr double SEG_PLACE_MIN_PRODUCTS = 4.0e9;
+inline bool placed_segments(const spg_plan_s& p) {
+    if (!packed_segments(p) || p.B.rows <= 0 || p.B.cols <= 0) return false;
+    const char* e = std::getenv("SPG_SEG_PLACE");
+    if (e && (std::strcmp(e, "1") == 0 || std::strcmp(e, "0") == 0)) return e[0] == '1';
+    const double avgB = (double)p.B.nnz / (double)p.B.rows;
+    const double seg = avgB * (double)(1 << p.tws) / (double)p.B.cols;
+    return seg * (double)brec_bytes(p.A.value_type) <= (double)SEG_PLACE_MAX &&
+           (double)p.A.nnz * avgB >= SEG_PLACE_MIN_PRODUCTS;
+}
+inline int64_t seg_blocks(const spg_plan_s& p) { return p.placed ? (int64_t)p.G * grid_for(p.B.rows, SEG_BLK) : 0; }
+// bytes of B's records before the sentinel records, at most
+inline size_t brec_span(const spg_plan_s& p) {
+    const size_t rb = brec_bytes(p.A.value_type);
+    if (!p.placed) return rb * (size_t)p.B.nnz;
+    return align_up((size_t)seg_bound((uint64_t)p.B.nnz, (uint64_t)p.B.rows * (uint64_t)p.G, (uint32_t)rb), SEG_LINE);
+}
 // fp64 8192-column sparse tiles (config 5's shape) run in cooperative record groups of
 // 1 << SP_RGS tiles (k_tile_sp<.., RG>), on a persistent grid of 8 / RG blocks per CU.
 // Measured on config 5 (round 5, numeric ms per product): RG 1 97.6 (511 GB of fabric reads per
@@ -694,6 +739,7 @@ inline bool alg1_upper_bound(const spg_plan_s& p) { return p.alg == SPG_ALG1 && 
 inline size_t status_words(const spg_plan_s& p) {
     return 2 * (size_t)(scan_tiles(p.A.rows) + 1) +
            (p.use_tile ? (size_t)scan_tiles(tile_items(p)) + 1 + (size_t)scan_tiles(bt_entries(p)) + 1 : 0) +
+           (p.placed ? (size_t)scan_tiles(seg_blocks(p)) + 1 : 0) +
            (fused_alg1(p) ? (size_t)std::max<int64_t>(grid_for(p.A.rows, ShortSmall::WPB), row_groups(p.A.rows)) + 1 : 0);
 }
 inline unsigned long long* rowptr_scan_status(const spg_plan_s& p) { return p.scan_status + scan_tiles(p.A.rows) + 1; }
@@ -702,6 +748,12 @@ inline unsigned long long* item_scan_status(const spg_plan_s& p) {
 }
 inline unsigned long long* bt_scan_status(const spg_plan_s& p) {
     return item_scan_status(p) + scan_tiles(tile_items(p)) + 1;
+}
+// (the end of B's records in bytes: behind the block lines and their total)
+inline int32_t* seg_end(const spg_plan_s& p) { return p.packed ? p.segblk + seg_blocks(p) + 1 : nullptr; }
+inline int seg_pairs(const spg_plan_s& p) { return p.placed ? PAIRS_PLACED : p.packed ? PAIRS_WRITE : PAIRS_NONE; }
+inline unsigned long long* seg_scan_status(const spg_plan_s& p) {   // (packed segments' block scan)
+    return bt_scan_status(p) + scan_tiles(bt_entries(p)) + 1;
 }
 
 // Offsets from the workspace pointer itself (spg_plan asks for no alignment slack).  The
@@ -718,7 +770,13 @@ Layout make_layout(const spg_plan_s& p) {
         L.tptr = c.take(sizeof(int32_t) * (size_t)(bt_entries(p) + 1));
         L.sidx = c.take(sizeof(uint32_t) * (size_t)p.B.rows * (size_t)(sym_tiles(p) + 1));
         // (B's records, then the lean kernels' sentinel records)
-        L.brec = c.take(brec_bytes(p.A.value_type) * (size_t)(p.B.nnz + SENT_REGIONS * SENT_N));
+        // (placed segments: the placed size's bound, and the slack to start the records at a line)
+        L.brec = c.take(brec_span(p) + brec_bytes(p.A.value_type) * (size_t)(SENT_REGIONS * SENT_N) +
+                        (p.placed ? SEG_LINE : 0));
+        if (p.packed) {
+            L.pseg = c.take(sizeof(uint2) * (size_t)p.B.rows * (size_t)p.G);
+            L.segblk = c.take(sizeof(int32_t) * (size_t)(seg_blocks(p) + 2));
+        }
         L.items = c.take(sizeof(int64_t) * (size_t)(tile_item_slots(p) + 1));
         // B's column indices modulo 65536 (the symbolic pass's columns: a symbolic tile never
         // crosses a 65536-aligned block)
@@ -757,6 +815,11 @@ void carve(spg_plan_s& p, const Layout& L) {
         p.sidx = (uint32_t*)(p.ws + L.sidx);
         p.tidx = (uint2*)(p.ws + L.bitmap);
         p.brec = (void*)(p.ws + L.brec);
+        if (p.placed) p.brec = (void*)(((uintptr_t)p.brec + SEG_LINE - 1) / SEG_LINE * SEG_LINE);
+        if (p.packed) {
+            p.pseg = (uint2*)(p.ws + L.pseg);
+            p.segblk = (int32_t*)(p.ws + L.segblk);
+        }
         p.bj16 = (uint16_t*)(p.ws + L.bj16);
         p.item_cnt = (int64_t*)(p.ws + L.items);
         p.bitmap = (uint32_t*)(p.ws + L.bitmap);
@@ -1001,6 +1064,19 @@ spg_status_t tile_build_index(spg_handle_t h, spg_plan_s& p) {
     spg_status_t st = launch_scan<int32_t, int32_t>(h, bt_entries(p), p.tptr, p.tptr, bt_scan_status(p),
                                                     p.scalars + 2, false);
     if (st) return st;
+    if (p.placed) {   // place the segments: block sizes, their scan, the pairs (k_seg_place)
+        const int64_t nblk = seg_blocks(p);
+        const dim3 grid((unsigned)std::max<int64_t>(1, grid_for(nblk, 256)));
+        const uint32_t rb = (uint32_t)brec_bytes(p.A.value_type);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_seg_place<false>, grid, dim3(256), p.B.rows, p.G, rb,
+                     (const int32_t*)p.tptr, p.segblk, p.pseg, (char*)p.brec);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<int32_t, int32_t>(h, nblk, p.segblk, p.segblk, seg_scan_status(p), p.scalars + 6, false)))
+            return st;
+        timed_launch(h, SPG_PHASE_LAYOUT, k_seg_place<true>, grid, dim3(256), p.B.rows, p.G, rb,
+                     (const int32_t*)p.tptr, p.segblk, p.pseg, (char*)p.brec);
+        SPG_LAUNCHED(h);
+    }
     p.tidx_built = true;
     return SPG_STATUS_SUCCESS;
 }
@@ -1092,7 +1168,7 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
         if (!p.brec_cols) {
             timed_launch(h, SPG_PHASE_LAYOUT, k_bt_pack<T, IP, 1>, dim3((unsigned)grid_for(p.B.rows, 4)), dim3(256),
                          p.B.rows, Bp, Bj, Bx, p.tws, (const int32_t*)p.tptr, (uint32_t*)p.brec, p.B.nnz, (T*)nullptr,
-                         p.rgs);
+                         p.rgs, p.pseg, seg_end(p), seg_pairs(p), p.G);
             SPG_LAUNCHED(h);
             p.brec_cols = true;
         }
@@ -1103,20 +1179,27 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
         const int64_t W = group_words(p);
         const int64_t q0 = g0 >> p.rgs, q1 = (g1 + (1 << p.rgs) - 1) >> p.rgs;
         const int64_t est = std::max<int64_t>(1, p.B.nnz * (q1 - q0) / std::max<int64_t>(rec_groups(p), 1));
-        timed_launch(h, SPG_PHASE_LAYOUT, k_bt_fill<T>,
-                     dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(est, 256), 16384))), dim3(256),
-                     tp + q0 * W, tp + (q1 - 1) * W + (W - 1), tm, (uint32_t*)p.brec);
+        if (p.placed)   // (RG = 1: groups are tiles) segment by segment
+            timed_launch(h, SPG_PHASE_LAYOUT, k_bt_fill_pk<T>,
+                         dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for((q1 - q0) * grid_for(p.B.rows, WAVE), 4), 16384))),
+                         dim3(256), p.B.rows, q0, q1, tp, (const uint2*)p.pseg, tm, (uint32_t*)p.brec);
+        else
+            timed_launch(h, SPG_PHASE_LAYOUT, k_bt_fill<T>,
+                         dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(grid_for(est, 256), 16384))), dim3(256),
+                         tp + q0 * W, tp + (q1 - 1) * W + (W - 1), tm, (uint32_t*)p.brec);
         SPG_LAUNCHED(h);
     } else if (!p.brec_built) {
         timed_launch(h, SPG_PHASE_LAYOUT, k_bt_pack<T, IP>, dim3((unsigned)grid_for(p.B.rows, 4)), dim3(256), p.B.rows,
-                     Bp, Bj, Bx, p.tws, (const int32_t*)p.tptr, (uint32_t*)p.brec, p.B.nnz, (T*)nullptr, p.rgs);
+                     Bp, Bj, Bx, p.tws, (const int32_t*)p.tptr, (uint32_t*)p.brec, p.B.nnz, (T*)nullptr, p.rgs,
+                     p.pseg, seg_end(p), seg_pairs(p), p.G);
         SPG_LAUNCHED(h);
         p.brec_built = true;
         p.brec_cols = true;
     }
-    // byte offset of sentinel region r after B's records (k_bt_pack)
+    // byte offset of sentinel region r after B's records (k_bt_pack); segment pairs: after
+    // the records' end, which the kernel reads on the device (*seg_end)
     auto sent = [&](int r) {
-        return (uint32_t)(((uint64_t)p.B.nnz + (uint64_t)r * SENT_N) * (uint64_t)rec_bytes<T>());
+        return (uint32_t)(((uint64_t)(p.packed ? 0 : p.B.nnz) + (uint64_t)r * SENT_N) * (uint64_t)rec_bytes<T>());
     };
     const int64_t nch = tile_chunks(p);
     for (int64_t c = 0; c < nch; ++c) {
@@ -1141,12 +1224,12 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
                                   (const int64_t*)tile_chunk_items(p, c), cj, cx, alpha, it_lo, it_hi, p.rgs);
         };
         if constexpr (std::is_same<T, float>::value) {
-            if (dense && fp32_runs(p)) {   // fp32 dense tiles of long B segments: entry runs
+            if (dense && p.packed) {   // fp32 dense tiles of long B segments: entry runs (fp32_runs)
                 hipExtLaunchKernelGGL((k_tile_dn<T, IP, 1024>), dim3(tile_grid(nit, DN_WPB)), dim3(DN_WPB * WAVE),
                                       0, h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, Ap, Aj, Ax, p.B.rows,
-                                      (const uint32_t*)p.brec, (const int32_t*)p.tptr,
+                                      (const uint32_t*)p.brec, (const uint2*)p.pseg, (const int32_t*)seg_end(p),
                                       (const int64_t*)tile_chunk_items(p, c), cj, cx, alpha,
-                                      sent(sentinel_region(1024)), it_lo, it_hi, p.rgs);
+                                      sent(sentinel_region(1024)), it_lo, it_hi);
                 SPG_LAUNCHED(h);
                 continue;
             }
@@ -1187,9 +1270,9 @@ spg_status_t tile_numeric(spg_handle_t h, spg_plan_s& p, int32_t* cj, T* cx, T a
                     constexpr int TWD = decltype(twd)::value;
                     hipExtLaunchKernelGGL((k_tile_dn<T, IP, TWD>), dim3(tile_grid(nit, DN_WPB)), dim3(DN_WPB * WAVE),
                                           0, h->stream, kt.a, kt.b, 0, r0, n, p.tws, p.G, Ap, Aj, Ax, p.B.rows,
-                                          (const uint32_t*)p.brec, (const int32_t*)p.tptr,
+                                          (const uint32_t*)p.brec, (const uint2*)p.pseg, (const int32_t*)seg_end(p),
                                           (const int64_t*)tile_chunk_items(p, c), cj, cx, alpha,
-                                          sent(sentinel_region(TWD)), it_lo, it_hi, p.rgs);
+                                          sent(sentinel_region(TWD)), it_lo, it_hi);
                 };
                 if constexpr (std::is_same<T, double>::value) {
                     if ((1 << p.tws) > 1024) dn(std::integral_constant<int, 2048>{});
@@ -2206,6 +2289,8 @@ spg_status_t spg_plan(spg_handle_t h, const spg_csr_t* A, const spg_csr_t* B, sp
     if (tmp.use_tile) {
         tmp.twss = sym_tile_log2(*B, tmp.tws, &tmp.sym_seg);
         tmp.rgs = record_group_log2(tmp);
+        tmp.packed = packed_segments(tmp);
+        tmp.placed = placed_segments(tmp);
         tmp.sym_flags = want_sym_flags(tmp);
     }
     // the general kernel's launch over the spill list (rows the short kernels hand over: A
@@ -2405,7 +2490,8 @@ spg_status_t spg_tile_values(spg_handle_t h, spg_plan_t p, void* tm) {
             using IP = decltype(ip);
             timed_launch(h, SPG_PHASE_LAYOUT, k_bt_pack<T, IP, 2>, dim3((unsigned)grid_for(p->B.rows, 4)), dim3(256),
                          p->B.rows, (const IP*)p->B.indptr, (const int32_t*)p->B.indices, (const T*)p->B.values,
-                         p->tws, (const int32_t*)p->tptr, (uint32_t*)p->brec, p->B.nnz, (T*)tm, p->rgs);
+                         p->tws, (const int32_t*)p->tptr, (uint32_t*)p->brec, p->B.nnz, (T*)tm, p->rgs,
+                         (uint2*)nullptr, (int32_t*)nullptr, PAIRS_NONE, p->G);   // (values by compact rank)
             SPG_LAUNCHED(h);
             return SPG_STATUS_SUCCESS;
         });

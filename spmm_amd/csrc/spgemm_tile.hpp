@@ -11,6 +11,7 @@
 // bitmap words, re-reading their products.
 #pragma once
 
+#include "seg_place.hpp"
 #include "spgemm_kernels.hpp"
 
 namespace spg {
@@ -163,10 +164,13 @@ __device__ __forceinline__ void load_rec_at(const char* __restrict__ rb, uint32_
     }
 }
 
+// Record stores at a byte address `q` of the record array (2-byte aligned for the 6- and 10-byte
+// forms, 4-byte aligned otherwise): the compact layout's record i is at byte i * rec_bytes, a
+// packed segment's at its placed offset (seg_place below).
 template <typename T>
-__device__ __forceinline__ void store_rec(uint32_t* __restrict__ rec, int64_t i, int lc, T v) {
+__device__ __forceinline__ void store_rec_at(char* __restrict__ q8, int lc, T v) {
     if constexpr (rec_bytes<T>() == 6) {   // three 2-byte stores
-        uint16_t* q = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + i * 6);
+        uint16_t* q = reinterpret_cast<uint16_t*>(q8);
         const uint32_t b = __float_as_uint(v);
         q[0] = (uint16_t)b;
         q[1] = (uint16_t)(b >> 16);
@@ -174,7 +178,7 @@ __device__ __forceinline__ void store_rec(uint32_t* __restrict__ rec, int64_t i,
         return;
     }
     if constexpr (rec_bytes<T>() == 10) {   // five 2-byte stores (a record is 2-byte aligned)
-        uint16_t* q = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + i * 10);
+        uint16_t* q = reinterpret_cast<uint16_t*>(q8);
         uint64_t b;
         __builtin_memcpy(&b, &v, 8);
 #pragma unroll
@@ -183,7 +187,7 @@ __device__ __forceinline__ void store_rec(uint32_t* __restrict__ rec, int64_t i,
         return;
     }
     constexpr int W = rec_words<T>();
-    uint32_t* q = rec + i * W;
+    uint32_t* q = reinterpret_cast<uint32_t*>(q8);
     __builtin_memcpy(q, &v, sizeof(T));
     q[W - 1] = (uint32_t)lc;
 }
@@ -191,31 +195,44 @@ __device__ __forceinline__ void store_rec(uint32_t* __restrict__ rec, int64_t i,
 // The column part / the value part of a record alone (spg_numeric_tiles: columns from B's
 // structure first, values group by group as they arrive).
 template <typename T>
-__device__ __forceinline__ void store_rec_col(uint32_t* __restrict__ rec, int64_t i, int lc) {
+__device__ __forceinline__ void store_rec_col_at(char* __restrict__ q8, int lc) {
     if constexpr (rec_bytes<T>() == 6) {
-        reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + i * 6)[2] = (uint16_t)lc;
+        reinterpret_cast<uint16_t*>(q8)[2] = (uint16_t)lc;
     } else if constexpr (rec_bytes<T>() == 10) {
-        reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + i * 10)[4] = (uint16_t)lc;
+        reinterpret_cast<uint16_t*>(q8)[4] = (uint16_t)lc;
     } else {
-        rec[i * rec_words<T>() + rec_words<T>() - 1] = (uint32_t)lc;
+        reinterpret_cast<uint32_t*>(q8)[rec_words<T>() - 1] = (uint32_t)lc;
     }
 }
 template <typename T>
-__device__ __forceinline__ void store_rec_val(uint32_t* __restrict__ rec, int64_t i, T v) {
+__device__ __forceinline__ void store_rec_val_at(char* __restrict__ q8, T v) {
     if constexpr (rec_bytes<T>() == 6) {
-        uint16_t* q = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + i * 6);
+        uint16_t* q = reinterpret_cast<uint16_t*>(q8);
         const uint32_t b = __float_as_uint(v);
         q[0] = (uint16_t)b;
         q[1] = (uint16_t)(b >> 16);
     } else if constexpr (rec_bytes<T>() == 10) {
-        uint16_t* q = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(rec) + i * 10);
+        uint16_t* q = reinterpret_cast<uint16_t*>(q8);
         uint64_t b;
         __builtin_memcpy(&b, &v, 8);
 #pragma unroll
         for (int h = 0; h < 4; ++h) q[h] = (uint16_t)(b >> (16 * h));
     } else {
-        __builtin_memcpy(rec + i * rec_words<T>(), &v, sizeof(T));
+        __builtin_memcpy(q8, &v, sizeof(T));
     }
+}
+// ... of record i of the compact layout
+template <typename T>
+__device__ __forceinline__ void store_rec(uint32_t* __restrict__ rec, int64_t i, int lc, T v) {
+    store_rec_at<T>(reinterpret_cast<char*>(rec) + i * rec_bytes<T>(), lc, v);
+}
+template <typename T>
+__device__ __forceinline__ void store_rec_col(uint32_t* __restrict__ rec, int64_t i, int lc) {
+    store_rec_col_at<T>(reinterpret_cast<char*>(rec) + i * rec_bytes<T>(), lc);
+}
+template <typename T>
+__device__ __forceinline__ void store_rec_val(uint32_t* __restrict__ rec, int64_t i, T v) {
+    store_rec_val_at<T>(reinterpret_cast<char*>(rec) + i * rec_bytes<T>(), v);
 }
 
 // Sentinel records after B's nnz records: the lean tile kernels point every product slot past
@@ -277,23 +294,90 @@ __global__ __launch_bounds__(256) void k_bt_count(int64_t K, int Gp, int G, int 
     }
 }
 
+// Segment pairs (plans whose numeric kernel is k_tile_dn: dense tiles, RG = 1).  The kernel finds
+// tile g's segment of B row k through `pseg`, one 8-byte {byte offset, record count} pair per
+// (tile, B row) at g * K + k, and the end of B's records (the sentinels' place) in a device word,
+// in bytes.  The scanned table `tptr` stays: it gives the lengths and the tile-major value order
+// (spg_tile_values) everywhere.  Where the expected segment is long (several lines: nothing to
+// save), the offsets are the compact ones, RB x (the segment's compact rank), and k_bt_pack writes
+// the pairs as it goes (PAIRS_WRITE).  Where it is short (at most SEG_PLACE_MAX bytes), the
+// segments are placed by seg_place (PAIRS_PLACED).  Placed offsets come from three passes: one lane places a block of SEG_BLK consecutive B rows of one
+// tile from offset 0 and reports the block's size in lines (k_seg_place<false>), a scan over the
+// block sizes gives every block's first line (and, in its last word, the end of all records in
+// lines; k_seg_place<true> puts it in bytes into the word behind), and the same walk again writes
+// the pairs and zeroes the bytes it skipped (k_seg_place<true>; a record load may overlap them,
+// nothing multiplies them).
+constexpr int PAIRS_NONE = 0, PAIRS_PLACED = 1, PAIRS_WRITE = 2;
+template <bool WRITE>
+__global__ __launch_bounds__(256) void k_seg_place(int64_t K, int G, uint32_t rb, const int32_t* __restrict__ tptr,
+                                                   int32_t* __restrict__ blk, uint2* __restrict__ pseg,
+                                                   char* __restrict__ rec) {
+    const int64_t nb = (K + SEG_BLK - 1) / SEG_BLK;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nb * G; i += (int64_t)gridDim.x * 256) {
+        if (WRITE && i == 0) blk[nb * G + 1] = (int32_t)((uint32_t)blk[nb * G] * SEG_LINE);   // records' end, bytes
+        const int64_t g = i / nb, k0 = (i - g * nb) * SEG_BLK;
+        const int n = (int)(K - k0 < SEG_BLK ? K - k0 : SEG_BLK);
+        const int32_t* __restrict__ tp = tptr + g * (K + 1) + k0;
+        const uint32_t base = WRITE ? (uint32_t)blk[i] * SEG_LINE : 0u;
+        // (the block's table words first, all loads in flight: the walk below is serial)
+        int32_t w[SEG_BLK + 1];
+#pragma unroll
+        for (int j = 0; j <= SEG_BLK; ++j) w[j] = tp[j < n ? j : n];
+        uint32_t x = 0;
+        int32_t s = w[0];
+#pragma unroll
+        for (int j = 0; j < SEG_BLK; ++j) {   // (rows past the table's end: length 0, nothing moves)
+            const int32_t e = w[j + 1];
+            const uint32_t L = (uint32_t)(e - s) * rb, at = seg_place(x, L);
+            if constexpr (WRITE) {
+                if (j < n) pseg[g * K + k0 + j] = make_uint2(base + at, (uint32_t)(e - s));
+                for (uint32_t q = x; q < at; q += 2) *reinterpret_cast<uint16_t*>(rec + base + q) = 0;
+            }
+            x = at + L;
+            s = e;
+        }
+        const uint32_t end = (x + SEG_LINE - 1) / SEG_LINE;
+        if constexpr (WRITE) {
+            for (uint32_t q = x; q < end * SEG_LINE; q += 2) *reinterpret_cast<uint16_t*>(rec + base + q) = 0;
+        } else {
+            blk[i] = (int32_t)end;
+        }
+    }
+}
+
 // One wave per B row: an entry's rank inside its tile segment is its distance to the
 // segment's first entry, found by a max-scan over the lanes where the tile id steps.
 // (The grid's first SENT_REGIONS * SENT_N threads also write the sentinel records after the
 // nnz(B) real ones.)
 // MODE 0: whole records; 1: the column parts and the sentinels only (values come later,
 // k_bt_fill); 2: the values alone, densely in record order into `tm` (spg_tile_values).
+// Segment pairs (`pairs`, RG = 1; MODE 2 is the same either way): PAIRS_PLACED, a record goes to
+// its segment's placed offset pseg[].x and the sentinels behind byte *pend; PAIRS_WRITE, records
+// and sentinels at their compact places as without pairs, and the wave of B row k writes the row's
+// G pairs {RB x compact rank, count} and one thread *pend = RB x nnz(B) for the numeric kernel.
 template <typename T, typename IP, int MODE = 0>
 __global__ __launch_bounds__(256) void k_bt_pack(int64_t K, const IP* __restrict__ Bp, const int32_t* __restrict__ Bj,
                                                  const T* __restrict__ Bx, int tws,
                                                  const int32_t* __restrict__ tptr, uint32_t* __restrict__ rec,
-                                                 int64_t nnzB, T* __restrict__ tm, int rgs) {
+                                                 int64_t nnzB, T* __restrict__ tm, int rgs,
+                                                 uint2* __restrict__ pseg, int32_t* __restrict__ pend, int pairs,
+                                                 int G) {
+    constexpr int RB = rec_bytes<T>();
     const int l = lane_id();
-    if (MODE != 2)
+    const bool pk = MODE != 2 && pairs == PAIRS_PLACED;
+    if (MODE != 2) {
+        const int64_t sb = pk ? (int64_t)(uint32_t)*pend : nnzB * RB;
+        if (pairs == PAIRS_WRITE && blockIdx.x == 0 && threadIdx.x == 0) *pend = (int32_t)(uint32_t)(nnzB * RB);
         for (int i = blockIdx.x * 256 + threadIdx.x; i < SENT_REGIONS * SENT_N; i += gridDim.x * 256)
-            store_rec(rec, nnzB + i, sentinel_col(i), (T)0);
+            store_rec_at<T>(reinterpret_cast<char*>(rec) + sb + (int64_t)i * RB, sentinel_col(i), (T)0);
+    }
     const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (k >= K) return;
+    if (MODE != 2 && pairs == PAIRS_WRITE)
+        for (int g = l; g < G; g += WAVE) {
+            const int32_t a = tptr[(int64_t)g * (K + 1) + k], b = tptr[(int64_t)g * (K + 1) + k + 1];
+            pseg[(int64_t)g * K + k] = make_uint2((uint32_t)a * (uint32_t)RB, (uint32_t)(b - a));
+        }
     const IP r0 = Bp[k];
     const int len = (int)(Bp[k + 1] - r0);
     int carry = 0;   // first entry of the segment the previous chunk ended in
@@ -307,9 +391,11 @@ __global__ __launch_bounds__(256) void k_bt_pack(int64_t K, const IP* __restrict
         const int s0 = max(wave_incl_max_dpp((in && g != gp) ? e : -1), carry);
         carry = readlane_i(s0, WAVE - 1);
         if (in) {
-            const int64_t at = (int64_t)tptr[tile_table_off(g, K, rgs) + (k << rgs)] + (e - s0);
-            if constexpr (MODE == 0) store_rec(rec, at, c & ((1 << tws) - 1), Bx[r0 + e]);
-            else if constexpr (MODE == 1) store_rec_col<T>(rec, at, c & ((1 << tws) - 1));
+            // byte offset of the record: its segment's placed start, or RB x its compact rank
+            const int64_t at = pk ? (int64_t)pseg[(int64_t)g * K + k].x + (int64_t)(e - s0) * RB
+                                  : ((int64_t)tptr[tile_table_off(g, K, rgs) + (k << rgs)] + (e - s0)) * (MODE == 2 ? 1 : RB);
+            if constexpr (MODE == 0) store_rec_at<T>(reinterpret_cast<char*>(rec) + at, c & ((1 << tws) - 1), Bx[r0 + e]);
+            else if constexpr (MODE == 1) store_rec_col_at<T>(reinterpret_cast<char*>(rec) + at, c & ((1 << tws) - 1));
             else tm[at] = Bx[r0 + e];
         }
     }
@@ -324,6 +410,32 @@ __global__ __launch_bounds__(256) void k_bt_fill(const int32_t* __restrict__ lo,
     for (int64_t r = r0 + (int64_t)blockIdx.x * 256 + threadIdx.x; r < r1; r += (int64_t)gridDim.x * 256)
         store_rec_val<T>(rec, r, tm[r]);
 }
+// ... of placed segments, tiles [g0, g1): a wave per 64 segments of a tile -- each lane reads one
+// segment's pair and compact rank, then the wave takes the segments in turn, lane j the value
+// tptr-rank + j of `tm` into record j at the placed offset (adjacent lanes, adjacent records)
+template <typename T>
+__global__ __launch_bounds__(256) void k_bt_fill_pk(int64_t K, int64_t g0, int64_t g1, const int32_t* __restrict__ tptr,
+                                                    const uint2* __restrict__ pseg, const T* __restrict__ tm,
+                                                    uint32_t* __restrict__ rec) {
+    constexpr int RB = rec_bytes<T>();
+    const int l = lane_id();
+    const int64_t nb = (K + WAVE - 1) / WAVE, n = (g1 - g0) * nb;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * 4) {
+        const int64_t g = g0 + i / nb, k = (i % nb) * WAVE + l;
+        uint2 se = make_uint2(0u, 0u);
+        int32_t r = 0;
+        if (k < K) {
+            se = pseg[g * K + k];
+            r = tptr[g * (K + 1) + k];
+        }
+        for (int q = 0; q < WAVE; ++q) {
+            const uint32_t off = (uint32_t)readlane_i((int)se.x, q), cnt = (uint32_t)readlane_i((int)se.y, q);
+            const int64_t r0 = readlane_i(r, q);
+            for (uint32_t j = l; j < cnt; j += WAVE)
+                store_rec_val_at<T>(reinterpret_cast<char*>(rec) + off + (int64_t)j * RB, tm[r0 + j]);
+        }
+    }
+}
 
 // (start, end) of B row k's segment in a tile (tp = tptr + tile_table_off(g, ..)): two
 // adjacent table words with one 8-byte load (4-byte aligned: one request instead of two)
@@ -331,6 +443,17 @@ __device__ __forceinline__ uint2 seg_pair(const int32_t* __restrict__ tp, int32_
     uint2 v;
     __builtin_memcpy(&v, tp + ((int64_t)k << rgs), sizeof(v));
     return v;
+}
+// ... of a tile with packed segments (pp = pseg + g * K): {byte offset of the segment in the
+// record array, its record count}, one aligned 8-byte load
+__device__ __forceinline__ uint2 seg_pair(const uint2* __restrict__ pp, int32_t k, int) { return pp[k]; }
+// record count and byte offset of a segment from either form of pair (RB = bytes per record)
+template <typename TP> constexpr bool seg_packed() { return std::is_same<TP, const uint2*>::value; }
+template <typename TP> __device__ __forceinline__ int seg_count(uint2 se) {
+    return seg_packed<TP>() ? (int)se.y : (int)(se.y - se.x);
+}
+template <typename TP> __device__ __forceinline__ uint32_t seg_bytes_at(uint2 se, uint32_t RB) {
+    return seg_packed<TP>() ? se.x : se.x * RB;
 }
 
 // Blocks are dispatched round-robin over the 8 XCDs.  Logical block ids that keep

@@ -297,8 +297,8 @@ __device__ __forceinline__ void dn_batch(L* lp, T* acc, int l, int cnt, uint32_t
 }
 
 // Batch b's entries (the first NB batches from the register queue `sq`/`aq`, the rest loaded).
-template <typename T, int NB>
-__device__ __forceinline__ void dn_fetch(int b, int l, const int32_t* __restrict__ tp, int64_t a0, int nA, T (&aq)[NB],
+template <typename T, int NB, typename TP>
+__device__ __forceinline__ void dn_fetch(int b, int l, TP tp, int64_t a0, int nA, T (&aq)[NB],
                                          uint2 (&sq)[NB], const int32_t* __restrict__ Aj, const T* __restrict__ Ax,
                                          int rgs, int& cnt, uint32_t& bb, T& av) {
     constexpr uint32_t RB = (uint32_t)rec_bytes<T>();
@@ -308,8 +308,8 @@ __device__ __forceinline__ void dn_fetch(int b, int l, const int32_t* __restrict
     if (b < NB * WAVE) {
         // the preloaded batches queue in registers: take the head, shift the rest down
         // (static register indices: a select chain or a dynamic index costs more)
-        cnt = (int)(sq[0].y - sq[0].x);
-        bb = sq[0].x * RB;
+        cnt = seg_count<TP>(sq[0]);
+        bb = seg_bytes_at<TP>(sq[0], RB);
         av = aq[0];
 #pragma unroll
         for (int q = 0; q + 1 < NB; ++q) {
@@ -318,16 +318,17 @@ __device__ __forceinline__ void dn_fetch(int b, int l, const int32_t* __restrict
         }
     } else if (b + l < nA) {
         const uint2 se = seg_pair(tp, Aj[a0 + b + l], rgs);
-        cnt = (int)(se.y - se.x);
-        bb = se.x * RB;
+        cnt = seg_count<TP>(se);
+        bb = seg_bytes_at<TP>(se, RB);
         av = Ax[a0 + b + l];
     }
 }
 
 // The ordered product walk of one item (row, tile): its A entries in batches of 64 (the first
 // NB batches' tile segments `sq` and values `aq` given, the rest loaded here), one dn_batch each.
-template <typename T, int NB, int MKB, typename L, typename Slot, typename Hit>
-__device__ __forceinline__ void dn_walk(L* lp, T* acc, int l, const int32_t* __restrict__ tp, int64_t a0, int nA,
+// (TP: the tile's segment table, const int32_t* scanned words or const uint2* packed pairs)
+template <typename T, int NB, int MKB, typename TP, typename L, typename Slot, typename Hit>
+__device__ __forceinline__ void dn_walk(L* lp, T* acc, int l, TP tp, int64_t a0, int nA,
                                         T (&aq)[NB], uint2 (&sq)[NB], const int32_t* __restrict__ Aj,
                                         const T* __restrict__ Ax, const char* __restrict__ rb, uint32_t sent,
                                         int rgs, Slot&& slot, Hit&& hit) {
@@ -335,7 +336,7 @@ __device__ __forceinline__ void dn_walk(L* lp, T* acc, int l, const int32_t* __r
         int cnt;
         uint32_t bb;
         T av;
-        dn_fetch<T, NB>(b, l, tp, a0, nA, aq, sq, Aj, Ax, rgs, cnt, bb, av);
+        dn_fetch<T, NB, TP>(b, l, tp, a0, nA, aq, sq, Aj, Ax, rgs, cnt, bb, av);
         dn_batch<T, MKB>(lp, acc, l, cnt, bb, av, rb, sent, slot, hit);
     }
 }
@@ -343,10 +344,10 @@ __device__ __forceinline__ void dn_walk(L* lp, T* acc, int l, const int32_t* __r
 // The item's output: its structure 64 columns at a time from hit[] or (dn_sent) the slots that
 // left -0.0 (ballot + lane rank give positions), straight to C; the rare -0.0 re-walk.
 template <typename T, int TWD>
-__device__ __forceinline__ void dn_emit(DnLds<T, TWD>& S, int l, int TW, int lo, int nnz, const int32_t* __restrict__ tp,
+__device__ __forceinline__ void dn_emit(DnLds<T, TWD>& S, int l, int TW, int lo, int nnz, const uint2* __restrict__ tp,
                                         int64_t a0, int nA, const int32_t* __restrict__ Aj,
                                         const char* __restrict__ rb, int32_t* __restrict__ crow,
-                                        T* __restrict__ xrow, T alpha, int rgs) {
+                                        T* __restrict__ xrow, T alpha) {
     constexpr uint32_t RB = (uint32_t)rec_bytes<T>();
     wsync();
     // the item's structure, 64 columns at a time: hit[] or (dn_sent) the non -0.0 slots
@@ -385,11 +386,11 @@ __device__ __forceinline__ void dn_emit(DnLds<T, TWD>& S, int l, int TW, int lo,
             // reached -0.0 slot into +0.0, then write the item again.
             for (int b = 0; b < nA; b += WAVE) {
                 if (b + l < nA) {
-                    const uint2 se = seg_pair(tp, Aj[a0 + b + l], rgs);
-                    for (uint32_t i = se.x; i < se.y; ++i) {
+                    const uint2 se = seg_pair(tp, Aj[a0 + b + l], 0);   // (byte offset, count)
+                    for (uint32_t i = 0; i < se.y; ++i) {
                         int c;
                         T v;
-                        load_rec(reinterpret_cast<const uint32_t*>(rb + (uint64_t)i * RB), 0, c, v);
+                        load_rec(reinterpret_cast<const uint32_t*>(rb + ((uint64_t)se.x + (uint64_t)i * RB)), 0, c, v);
                         if (is_neg_zero(S.acc[c])) S.acc[c] = (T)0;
                     }
                 }
@@ -420,18 +421,18 @@ __device__ __forceinline__ void dn_clear(DnLds<T, TWD>& S, int l, int TW) {
 // One dense-tile item (row, tile g of TW <= TWD columns) on one wave: clear the accumulator,
 // the ordered product walk with slot = column, then the output.
 template <typename T, int NB, int TWD>
-__device__ __forceinline__ void dn_item(DnLds<T, TWD>& S, int l, int TW, int lo, int nnz, const int32_t* __restrict__ tp,
+__device__ __forceinline__ void dn_item(DnLds<T, TWD>& S, int l, int TW, int lo, int nnz, const uint2* __restrict__ tp,
                                         int64_t a0, int nA, T (&aq)[NB], uint2 (&sq)[NB],
                                         const int32_t* __restrict__ Aj,
                                         const T* __restrict__ Ax, const char* __restrict__ rb, uint32_t sent,
                                         int32_t* __restrict__ crow,
-                                        T* __restrict__ xrow, T alpha, int rgs) {
+                                        T* __restrict__ xrow, T alpha) {
     dn_clear(S, l, TW);
-    dn_walk<T, NB, dn_mkb(TWD)>(&S, S.acc, l, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, rgs, [&](int c) { return c; },
+    dn_walk<T, NB, dn_mkb(TWD), const uint2*>(&S, S.acc, l, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, 0, [&](int c) { return c; },
                    [&](int c) {
                        if constexpr (!dn_sent<T>()) S.hit[c] = 1;
                    });
-    dn_emit<T, TWD>(S, l, TW, lo, nnz, tp, a0, nA, Aj, rb, crow, xrow, alpha, rgs);
+    dn_emit<T, TWD>(S, l, TW, lo, nnz, tp, a0, nA, Aj, rb, crow, xrow, alpha);
 }
 // Numeric pass on dense tiles: one wave per (row, tile) item, items tile-major over the
 // XCD-aware block map (an XCD works through one tile at a time, so the tile's B slice and
@@ -443,10 +444,12 @@ template <typename T, typename IP, int TWD>
 __global__ __launch_bounds__(DN_WPB * WAVE) void k_tile_dn(
     int64_t row0, int64_t nrows, int tws, int G, const IP* __restrict__ Ap,
     const int32_t* __restrict__ Aj, const T* __restrict__ Ax, int64_t K,
-    const uint32_t* __restrict__ brec, const int32_t* __restrict__ tptr,
-    const int64_t* __restrict__ item_off, int32_t* __restrict__ Cj, T* __restrict__ Cx, T alpha, uint32_t sent,
-    uint32_t it_lo, uint32_t it_hi, int rgs) {
+    const uint32_t* __restrict__ brec, const uint2* __restrict__ pseg, const int32_t* __restrict__ pend,
+    const int64_t* __restrict__ item_off, int32_t* __restrict__ Cj, T* __restrict__ Cx, T alpha, uint32_t sent_r,
+    uint32_t it_lo, uint32_t it_hi) {
     static_assert(OrderedLdsAdd<T>::value || std::is_same<T, float>::value, "ordered LDS add or fp32 runs");
+    // the kernel's sentinel region: `sent_r` bytes behind the end of B's records (*pend, in bytes)
+    const uint32_t sent = (uint32_t)uniform(*pend) + sent_r;
     constexpr int NB = sizeof(T) > 8 ? 4 : 8;    // A batches preloaded per item
     __shared__ __attribute__((aligned(16))) DnLds<T, TWD> lds[DN_WPB];
     const int l = lane_id();
@@ -462,7 +465,7 @@ __global__ __launch_bounds__(DN_WPB * WAVE) void k_tile_dn(
         const int64_t obase = ld_a(item_off + item);
         const int nnz = (int)(ld_a(item_off + item + 1) - obase);
         if (nnz == 0) continue;                      // (no product reaches this tile)
-        const int32_t* __restrict__ tp = tptr + tile_table_off(g, K, rgs);
+        const uint2* __restrict__ tp = pseg + (int64_t)g * K;   // tile g's segment pairs (dense tiles: RG = 1)
         const int64_t a0 = Ap[row];
         const int nA = (int)(Ap[row + 1] - a0);
         int32_t kq[NB];
@@ -478,9 +481,8 @@ __global__ __launch_bounds__(DN_WPB * WAVE) void k_tile_dn(
             }
         }
 #pragma unroll
-        for (int q = 0; q < NB; ++q) sq[q] = kq[q] >= 0 ? seg_pair(tp, kq[q], rgs) : make_uint2(0u, 0u);
-        dn_item<T, NB, TWD>(S, l, TW, g * TW, nnz, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, Cj + obase, Cx + obase, alpha,
-                            rgs);
+        for (int q = 0; q < NB; ++q) sq[q] = kq[q] >= 0 ? seg_pair(tp, kq[q], 0) : make_uint2(0u, 0u);
+        dn_item<T, NB, TWD>(S, l, TW, g * TW, nnz, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, Cj + obase, Cx + obase, alpha);
     }
 }
 
@@ -633,7 +635,7 @@ void k_tile_sp(
             wsync();
             for (int p = l; p < wn; p += WAVE) S.acc[p] = (T)0;
             if (L0 > 0) preload();   // (the walk consumes the queue; rare later windows reload it)
-            dn_walk<T, NB, CF::MKB>(&S, S.acc, l, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, rgs,
+            dn_walk<T, NB, CF::MKB, const int32_t*>(&S, S.acc, l, tp, a0, nA, aq, sq, Aj, Ax, rb, sent, rgs,
                            [&](int rc) -> int {
                                if (rc < clo || rc >= chi) return SP_CAP + (l & (SP_DUMMY - 1));   // (sentinels too)
                                const uint2 b = S.bw[rc >> 5];
