@@ -13,7 +13,8 @@ is row << bits(cols - 1) | column, 32 bits wide when it fits and 64 otherwise, s
 passes; the mark and value kernels run 256 sorted entries per workgroup and a run's head walks the
 whole run, whoever owns its tail.
 
-Not tested here: SPG_STATUS_OVERFLOW (nnz(C) past an int32 row pointer) needs 2**31 entries.
+Not tested here: SPG_STATUS_OVERFLOW (nnz(C) past an int32 row pointer) needs 2**31 entries;
+tests/test_gpu_large_offsets.py::test_canonicalize_sort_sum has them, built on the device.
 """
 import ctypes
 

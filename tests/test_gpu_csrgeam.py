@@ -11,7 +11,8 @@ The kernels' seams (spmm_amd/csrc/spgemm_geam.hpp): a wave walks its chunk of GM
 entries 64 at a time, a workgroup holds GM_WPB = 4 waves (4096 entries); a step whose 64 entries
 lie in one row searches a window of the other row; the two scans work in tiles of SCAN_TILE = 2048.
 
-Not tested here: SPG_STATUS_OVERFLOW (nnz(C) past an int32 row pointer) needs 2**31 entries.
+Not tested here: SPG_STATUS_OVERFLOW (nnz(C) past an int32 row pointer) needs 2**31 entries;
+tests/test_gpu_large_offsets.py::test_csrgeam has them, built on the device.
 
 The complex `mixed` cases of test_special_values are what tells (1, -1), the subtraction, from
 (2, -1): scipy's A - B subtracts part by part, while numpy's (-1) * B in (2*A) + (-1*B) is the
