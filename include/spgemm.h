@@ -354,6 +354,67 @@ spg_status_t spg_canonicalize_nnz(spg_handle_t handle, const spg_csr_t *A, const
 spg_status_t spg_canonicalize(spg_handle_t handle, const spg_csr_t *A, const int32_t *coo_rows,
                               unsigned ops, spg_csr_t *C, size_t workspace_bytes, void *workspace);
 
+/* Submatrix extraction: C = A[R, K], the rows R and the columns K of a CSR matrix, in two calls
+ * like the addition -- a structure pass that writes C's row pointer and returns nnz(C), then a
+ * value pass into the caller's C.  (cupyx's csr_matrix.__getitem__, which runs kernels of its own
+ * and no cuSPARSE call: cupy-src/cupyx/scipy/sparse/_index.py:348 (__getitem__) and :45-115
+ * (_get_csr_submatrix_major_axis, _get_csr_submatrix_minor_axis, _csr_row_index);
+ * _compressed.py:403 (_major_index_fancy), :566 (_minor_index_fancy), :643 (_major_slice) and
+ * :665 (_minor_slice).  Added within 0.2.0: a caller detects it by symbol lookup.)
+ *   Selections: an spg_sel_t per axis.  index == NULL: the sequence start + t*step for t in
+ *     [0, count), step != 0 unless count <= 1, any sign.  index != NULL: `count` device int32
+ *     entries in any order, repeats allowed; start and step are ignored.  A NULL spg_sel_t*
+ *     selects the whole axis.  List entries must lie in [0, extent) (not checked, like coo_rows).
+ *   The rule: with sel_r(0..nr-1) the selected source rows in the order asked for, output row i is
+ *     source row sel_r(i) walked in STORED order.  A need not be canonical: unsorted rows and
+ *     duplicate (row, column) entries are allowed and kept.  A stored entry (column j, value v)
+ *     gives, with K all columns: one entry (j, v); K a range (start, step, count): one entry
+ *     ((j - start) / step, v) iff step divides j - start and the quotient lies in [0, count),
+ *     nothing otherwise -- with a negative step the entries still stay in A's stored order, so a
+ *     canonical A gives descending columns, as scipy does (it routes stepped column slices
+ *     through its fancy path); K a list idx[0..k-1]: one entry (t, v) for every position t with
+ *     idx[t] == j, positions ascending.  Wherever every listed column is distinct that is scipy's
+ *     csr_column_index1 / csr_column_index2 array for array; where idx repeats a column scipy
+ *     orders the repeats by np.argsort(idx), which is not stable; ascending positions is the
+ *     stable choice.
+ *   Values are moved, never computed on: bit for bit, NaN sign and payload, -0.0 and denormals
+ *     included (the transpose's rule).
+ *   C is nr x nc of A's value type, nc = A->cols, the range's count or the list's length; its row
+ *     pointer may be int32 or int64 whatever A's is.  nnz(C) can exceed nnz(A) (repeated rows or
+ *     columns).  Identical from run to run: no global atomic places an entry, no position depends
+ *     on the order in which anything landed.
+ *   spg_csr_extract_nnz, workspace == NULL: size query, *workspace_bytes is set by host
+ *     arithmetic from A->nnz, A->cols and the counts, and nothing is launched.  workspace != NULL:
+ *     *workspace_bytes must be >= the queried size; writes C_indptr (nr + 1 entries of
+ *     C_indptr_type) and *nnzC, waiting for the device once, for nnzC.  SPG_STATUS_OVERFLOW when
+ *     nnzC does not fit an int32 C_indptr (*nnzC is still set: call again with an int64 array).
+ *     A's values are not read.
+ *   spg_csr_extract: takes the workspace exactly as spg_csr_extract_nnz left it, for the same A
+ *     and selections (the index lists unchanged); C->indptr is the array that call wrote,
+ *     C->indices / C->values hold C->nnz = nnzC entries.  Stream-ordered; does not wait.
+ *   Neither call allocates device memory: every device scalar lives in the workspace.
+ *   Status: NULL handle SPG_STATUS_NOT_INITIALIZED (checked first).  SPG_STATUS_INVALID_VALUE for
+ *     a NULL A, workspace_bytes or nnzC; a NULL C_indptr with a workspace; a C_indptr_type that is
+ *     neither index type; a workspace below the queried size (spg_csr_extract: or NULL); a
+ *     count < 0; step == 0 with count > 1; a range whose first or last member falls outside
+ *     [0, extent) (checked on the host); a NULL C; a C that is not nr x nc of A's value type; a
+ *     NULL array that is needed.  A rows->count, a cols->count or an A->cols above 2^31 - 1:
+ *     SPG_STATUS_NOT_SUPPORTED.
+ *   Degenerate sizes: nr == 0 or nc == 0 succeeds without a kernel (nr == 0 writes the single 0
+ *     of the row pointer); nnz(A) == 0 leaves an all-zero row pointer.
+ *   Aliasing: A and the index lists are only read; an output overlapping an input is undefined.
+ *   Timing: the mark and count kernels (k_ex_mark, k_ex_count) under SPG_PHASE_SYMBOLIC, the
+ *     scans under SPG_PHASE_SCAN, the column list's grouping (k_ex_pack, k_tr_hist, k_cn_scatter,
+ *     k_tr_indptr) under SPG_PHASE_LAYOUT, the value kernel (k_ex_fill) under SPG_PHASE_NUMERIC. */
+typedef struct { int64_t start, step, count; const int32_t *index; } spg_sel_t;
+
+spg_status_t spg_csr_extract_nnz(spg_handle_t handle, const spg_csr_t *A, const spg_sel_t *rows,
+                                 const spg_sel_t *cols, void *C_indptr, spg_index_t C_indptr_type,
+                                 int64_t *nnzC, size_t *workspace_bytes, void *workspace);
+spg_status_t spg_csr_extract(spg_handle_t handle, const spg_csr_t *A, const spg_sel_t *rows,
+                             const spg_sel_t *cols, spg_csr_t *C, size_t workspace_bytes,
+                             void *workspace);
+
 /* Sparse -> dense: D = A as a dense matrix, scipy's csr_todense (A.toarray()).  (cusparse<t>csr2dense
  * and cusparseSparseToDense as called by cupyx.cusparse.csr2dense, csc2dense and sparseToDense,
  * cupy-src/cupyx/cusparse.py:768-797, :800-829 and :1805-1833; cupyx's own kernel behind
@@ -538,11 +599,13 @@ typedef enum {
     SPG_PHASE_SCAN = 1,       /* k_scan_lb / k_items_to_rowptr: prefix sums       */
     SPG_PHASE_SYMBOLIC = 2,   /* k_row (count) / k_tile_sym(_seg) / k_symbolic;    */
                               /* spg_csrgeam_nnz's k_geam_mark / k_geam_count;     */
-                              /* spg_dense2csr_nnz's k_dn_count / k_dn_indptr      */
+                              /* spg_dense2csr_nnz's k_dn_count / k_dn_indptr;     */
+                              /* spg_csr_extract_nnz's k_ex_mark / k_ex_count      */
     SPG_PHASE_NUMERIC = 3,    /* k_row / k_tile_dn / k_tile_sp / k_tile /          */
                               /* k_numeric: values (ALG1 also structure); one       */
                               /* kernel per launch; spg_csrgeam's k_geam_fill;      */
-                              /* spg_dense2csr's k_dn_fill                          */
+                              /* spg_dense2csr's k_dn_fill; spg_csr_extract's       */
+                              /* k_ex_fill                                          */
     SPG_PHASE_COMPACT = 4,    /* k_compact: ALG1 copy into C                        */
     SPG_PHASE_VALIDATE = 5,   /* k_validate                                         */
     SPG_PHASE_SPILL = 6,      /* k_symbolic / k_numeric over the rows the short-row */
@@ -552,7 +615,8 @@ typedef enum {
                               /* (k_tile_index, k_bt_count, k_bj16, k_bt_pack) and   */
                               /* per tile group (k_bt_fill, spg_numeric_tiles);       */
                               /* spg_csr2csc's passes (k_tr_hist, k_tr_scatter);      */
-                              /* spg_csr2dense's k_csr2dense                          */
+                              /* spg_csr2dense's k_csr2dense; spg_csr_extract_nnz's   */
+                              /* grouping of a column list (k_ex_pack and the sort)   */
     SPG_NUM_PHASES = 9
 } spg_phase_t;
 

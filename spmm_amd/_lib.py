@@ -50,7 +50,7 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_spgemm_ws", "spg_plan_info", "spg_tile_value_offsets", "spg_tile_values",
            "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm", "spg_csr2csc",
            "spg_csrgeam_nnz", "spg_csrgeam", "spg_canonicalize_nnz", "spg_canonicalize",
-           "spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr")
+           "spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr", "spg_csr_extract_nnz", "spg_csr_extract")
 
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
@@ -68,6 +68,12 @@ class SpgDense(ctypes.Structure):
     """spg_dense_t"""
     _fields_ = [("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("ld", ctypes.c_int64),
                 ("values", ctypes.c_void_p), ("order", ctypes.c_int), ("value_type", ctypes.c_int)]
+
+
+class SpgSel(ctypes.Structure):
+    """spg_sel_t: start + t*step for t in [0, count), or ``count`` device int32 entries at ``index``"""
+    _fields_ = [("start", ctypes.c_int64), ("step", ctypes.c_int64), ("count", ctypes.c_int64),
+                ("index", ctypes.c_void_p)]
 
 
 class SpgPlanInfo(ctypes.Structure):
@@ -111,6 +117,7 @@ def load():
         vp, i64, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_size_t
         csrp = ctypes.POINTER(SpgCsr)
         dnp = ctypes.POINTER(SpgDense)
+        selp = ctypes.POINTER(SpgSel)
         proto = {
             "spg_version": (ctypes.c_int, []),
             "spg_build_info": (ctypes.c_char_p, []),
@@ -132,6 +139,9 @@ def load():
             "spg_canonicalize_nnz": (ctypes.c_int, [vp, csrp, vp, ctypes.c_uint, vp, ctypes.c_int,
                                                     ctypes.POINTER(i64), ctypes.POINTER(sz), vp]),
             "spg_canonicalize": (ctypes.c_int, [vp, csrp, vp, ctypes.c_uint, csrp, sz, vp]),
+            "spg_csr_extract_nnz": (ctypes.c_int, [vp, csrp, selp, selp, vp, ctypes.c_int, ctypes.POINTER(i64),
+                                                   ctypes.POINTER(sz), vp]),
+            "spg_csr_extract": (ctypes.c_int, [vp, csrp, selp, selp, csrp, sz, vp]),
             "spg_csr2dense": (ctypes.c_int, [vp, csrp, dnp]),
             "spg_dense2csr_nnz": (ctypes.c_int, [vp, dnp, vp, ctypes.c_int, ctypes.POINTER(i64),
                                                  ctypes.POINTER(sz), vp]),

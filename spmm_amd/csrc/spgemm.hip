@@ -27,6 +27,7 @@
 #include "spgemm_transpose.hpp"
 #include "spgemm_geam.hpp"
 #include "spgemm_canon.hpp"
+#include "spgemm_extract.hpp"
 #include "spgemm_dense.hpp"
 
 using namespace spg;
@@ -2116,6 +2117,179 @@ spg_status_t cn_dispatch(const spg_csr_t& A, const CnLayout& L, F&& f) {
     return dispatch_index(A.indptr_type, [&](auto ip) { return L.k64 ? f(ip, uint64_t(0)) : f(ip, uint32_t(0)); });
 }
 
+// ----------------------------------------------------------------------------- spg_csr_extract
+
+// One axis' selection after the host checks: a NULL spg_sel_t is the whole axis, a range of at
+// most one member has step 1.
+struct ExSel {
+    bool whole = true;
+    int64_t start = 0, step = 1, count = 0;
+    const int32_t* index = nullptr;
+};
+
+// `sel` over an axis of `extent` members, checked on the host (list entries are not read).
+spg_status_t ex_sel(const spg_sel_t* sel, int64_t extent, ExSel& out) {
+    out = ExSel{};
+    out.count = extent;
+    if (!sel) return SPG_STATUS_SUCCESS;
+    out.whole = false;
+    out.count = sel->count;
+    out.index = sel->index;
+    if (sel->count < 0) return SPG_STATUS_INVALID_VALUE;
+    if (sel->count > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;
+    if (sel->index) return SPG_STATUS_SUCCESS;
+    if (sel->count > 1 && sel->step == 0) return SPG_STATUS_INVALID_VALUE;
+    out.start = sel->start;
+    out.step = sel->count > 1 ? sel->step : 1;
+    if (sel->count > 0) {
+        const __int128 last = (__int128)out.start + (__int128)(out.count - 1) * out.step;
+        if (out.start < 0 || out.start >= extent || last < 0 || last >= extent) return SPG_STATUS_INVALID_VALUE;
+    }
+    return SPG_STATUS_SUCCESS;
+}
+
+// Workspace carve of spg_csr_extract_nnz / spg_csr_extract (offsets from the 256-byte aligned
+// base).  S, and with a column list colptr and the sorted records, stay for the value call.
+struct ExLayout {
+    int kmode = EX_ALL;
+    bool s64 = false;           // S is int64 (a column list, or A's row pointer is)
+    bool contig = false;        // K = all over a step-1 row range: one span of A
+    int passes = 0;             // sort passes over the listed columns' bits
+    int64_t kchunks = 0;        // wave chunks of TR_CHUNK list positions
+    size_t scalars = 0;         // 16 int64: [0] a scan's total, [1] its overflow flag
+    size_t status_e = 0, status_r = 0, status_t = 0;   // look-back words: over A's entries / the output rows / the sort's table
+    size_t S = 0;               // nnz(A) + 1 SP: mult, scanned in place
+    size_t cnt = 0;             // nr + 1 int64: entries per output row
+    size_t table = 0;           // 256 * kchunks + 1 int32: a pass's digit histogram, scanned in place
+    size_t colptr = 0;          // cols + 1 int32
+    size_t buf[2] = {0, 0};     // ping-pong records of the list (k_ex_pack writes buf[0])
+    size_t total = 0;           // bytes to ask for (256 of slack for the base alignment)
+};
+
+ExLayout ex_layout(const spg_csr_t& A, const ExSel& R, const ExSel& K) {
+    ExLayout L;
+    L.kmode = K.whole ? EX_ALL : K.index ? EX_LIST : EX_RANGE;
+    L.s64 = L.kmode == EX_LIST || A.indptr_type == SPG_INDEX_64I;
+    L.contig = L.kmode == EX_ALL && !R.index && R.step == 1;
+    Carver c;
+    L.scalars = c.take(16 * sizeof(int64_t));
+    L.status_r = c.take(status_bytes(R.count));
+    L.cnt = c.take(sizeof(int64_t) * ((size_t)R.count + 1));
+    if (L.kmode != EX_ALL) {
+        L.status_e = c.take(status_bytes(A.nnz));
+        L.S = c.take((L.s64 ? 8 : 4) * ((size_t)A.nnz + 1));
+    }
+    if (L.kmode == EX_LIST) {
+        L.passes = (index_bits(A.cols) + 7) / 8;
+        L.kchunks = (K.count + TR_CHUNK - 1) / TR_CHUNK;
+        L.status_t = c.take(status_bytes(TR_RADIX * L.kchunks));
+        L.table = c.take(sizeof(int32_t) * ((size_t)TR_RADIX * (size_t)L.kchunks + 1));
+        L.colptr = c.take(sizeof(int32_t) * ((size_t)A.cols + 1));
+        for (int b = 0; b < 2; ++b) L.buf[b] = c.take(sizeof(ExRec) * (size_t)K.count);
+    }
+    L.total = c.off + 256;
+    return L;
+}
+
+// what both entry points ask of A and the selections
+spg_status_t ex_check(const spg_csr_t* A, const spg_sel_t* rows, const spg_sel_t* cols, ExSel& R, ExSel& K) {
+    spg_status_t st = check_csr(A);
+    if (st) return st;
+    if ((st = ex_sel(rows, A->rows, R)) || (st = ex_sel(cols, A->cols, K))) return st;
+    return SPG_STATUS_SUCCESS;
+}
+
+ExCols ex_cols(const ExSel& K, const ExLayout& L, char* ws) {
+    ExCols c;
+    c.mode = L.kmode;
+    c.start = K.start;
+    c.step = K.step;
+    c.count = K.count;
+    c.colptr = L.kmode == EX_LIST ? (const int32_t*)(ws + L.colptr) : nullptr;
+    c.colpos = L.kmode == EX_LIST ? (const ExRec*)(ws + L.buf[L.passes & 1]) : nullptr;
+    return c;
+}
+
+// colptr and the grouped positions of a column list: spg_canonicalize's passes over the records
+// (listed column, position).
+spg_status_t ex_group(spg_handle_t h, const spg_csr_t& A, const ExSel& K, const ExLayout& L, char* ws) {
+    const int64_t k = K.count, chunks = L.kchunks;
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    unsigned long long* status = (unsigned long long*)(ws + L.status_t);
+    int32_t* table = (int32_t*)(ws + L.table);
+    timed_launch(h, SPG_PHASE_LAYOUT, k_ex_pack, dim3((unsigned)grid_for(k, EX_BLOCK)), dim3(EX_BLOCK), k, K.index,
+                 (ExRec*)(ws + L.buf[0]));
+    SPG_LAUNCHED(h);
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    for (int p = 0; p < L.passes; ++p) {
+        const int shift = 8 * p;
+        const ExRec* in = (const ExRec*)(ws + L.buf[p & 1]);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<int32_t, CnKeys<int32_t, uint32_t>>, grid, block, k, chunks,
+                     CnKeys<int32_t, uint32_t>{in, 0}, shift, table);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<int32_t, int32_t>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
+        timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<int32_t, uint32_t>, grid, block, k, chunks, shift, in,
+                     (const int32_t*)table, (ExRec*)(ws + L.buf[(p + 1) & 1]));
+        SPG_LAUNCHED(h);
+    }
+    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
+    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<int32_t, int32_t, CnKeys<int32_t, uint32_t>>, dim3(pgrid), dim3(256),
+                 k, A.cols, CnKeys<int32_t, uint32_t>{(const ExRec*)(ws + L.buf[L.passes & 1]), 0},
+                 (int32_t*)(ws + L.colptr), (const int32_t*)nullptr);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP, typename SP>
+spg_status_t ex_structure(spg_handle_t h, const spg_csr_t& A, const ExSel& R, const ExSel& K, const ExLayout& L,
+                          char* ws, CP* Cp, int64_t* nnzC) {
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    int64_t* cnt = (int64_t*)(ws + L.cnt);
+    SP* S = L.kmode == EX_ALL ? nullptr : (SP*)(ws + L.S);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if (L.kmode == EX_LIST && (st = ex_group(h, A, K, L, ws))) return st;
+    if (S) {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_ex_mark<SP>, dim3((unsigned)grid_for(A.nnz, EX_BLOCK)), dim3(EX_BLOCK),
+                     A.nnz, (const int32_t*)A.indices, ex_cols(K, L, ws), S);
+        SPG_LAUNCHED(h);
+        if ((st = launch_scan<SP, SP>(h, A.nnz, S, S, (unsigned long long*)(ws + L.status_e), scal, true))) return st;
+    }
+    const unsigned cgrid = (unsigned)std::min<int64_t>(grid_for(R.count, EX_BLOCK), 1 << 20);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_ex_count<IP, SP>, dim3(cgrid), dim3(EX_BLOCK), R.count,
+                 ExRows{R.index, R.start, R.step}, (const IP*)A.indptr, (const SP*)S, cnt);
+    SPG_LAUNCHED(h);
+    if ((st = launch_scan<CP, int64_t>(h, R.count, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
+        return st;
+    int64_t sc[2] = {0, 0};
+    if ((st = read_scalars(h, scal, 2, sc))) return st;
+    *nnzC = sc[0];
+    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename CP, typename SP, typename V>
+spg_status_t ex_values(spg_handle_t h, const spg_csr_t& A, const ExSel& R, const ExSel& K, spg_csr_t& C,
+                       const ExLayout& L, char* ws) {
+    const int64_t chunks = (C.nnz + EX_CHUNK - 1) / EX_CHUNK;
+    timed_launch(h, SPG_PHASE_NUMERIC, k_ex_fill<IP, CP, SP, V>, dim3((unsigned)grid_for(chunks, EX_WPB)),
+                 dim3(EX_WPB * WAVE), R.count, C.nnz, chunks, ExRows{R.index, R.start, R.step}, ex_cols(K, L, ws),
+                 L.contig, (const IP*)A.indptr, (const int32_t*)A.indices, (const V*)A.values,
+                 L.kmode == EX_ALL ? (const SP*)nullptr : (const SP*)(ws + L.S), (const CP*)C.indptr,
+                 (int32_t*)C.indices, (V*)C.values);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+// f(IP{}, SP{}): A's row-pointer type and S's (int64 for a column list)
+template <typename F>
+spg_status_t ex_dispatch(const spg_csr_t& A, const ExLayout& L, F&& f) {
+    return dispatch_index(A.indptr_type, [&](auto ip) {
+        using IP = decltype(ip);
+        if constexpr (sizeof(IP) == 8) return f(ip, int64_t{});
+        else return L.s64 ? f(ip, int64_t{}) : f(ip, int32_t{});
+    });
+}
+
 }  // namespace
 
 // ---- 16-bit columns for the structure broadcast (include/spgemm.h, spg_cols16_*)
@@ -2648,6 +2822,65 @@ spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, 
         std::memcpy(&be, beta, sizeof(T));
         return dispatch_index(A->indptr_type, C->indptr_type, [&](auto ip, auto cp) {
             return gm_values<decltype(ip), decltype(cp), T>(h, *A, *B, *C, L, ws_base(workspace), al, be);
+        });
+    });
+}
+
+spg_status_t spg_csr_extract_nnz(spg_handle_t h, const spg_csr_t* A, const spg_sel_t* rows, const spg_sel_t* cols,
+                                 void* C_indptr, spg_index_t C_indptr_type, int64_t* nnzC, size_t* workspace_bytes,
+                                 void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!A || !workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
+    ExSel R, K;
+    spg_status_t st = ex_check(A, rows, cols, R, K);
+    if (st) return st;
+    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const ExLayout L = ex_layout(*A, R, K);
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
+    if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    if (R.count == 0 || K.count == 0 || A->nnz == 0) {   // an all-zero row pointer (nr == 0: its one entry)
+        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type) * (size_t)(R.count + 1), h->stream));
+        *nnzC = 0;
+        return SPG_STATUS_SUCCESS;
+    }
+    return ex_dispatch(*A, L, [&](auto ip, auto sp) {
+        return dispatch_index(C_indptr_type, [&](auto cp) {
+            using CP = decltype(cp);
+            return ex_structure<decltype(ip), CP, decltype(sp)>(h, *A, R, K, L, ws_base(workspace), (CP*)C_indptr,
+                                                                 nnzC);
+        });
+    });
+}
+
+spg_status_t spg_csr_extract(spg_handle_t h, const spg_csr_t* A, const spg_sel_t* rows, const spg_sel_t* cols,
+                             spg_csr_t* C, size_t workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!A || !C || !workspace) return SPG_STATUS_INVALID_VALUE;
+    ExSel R, K;
+    spg_status_t st = ex_check(A, rows, cols, R, K);
+    if (st) return st;
+    if (C->rows != R.count || C->cols != K.count || C->value_type != A->value_type || C->nnz < 0)
+        return SPG_STATUS_INVALID_VALUE;
+    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    const ExLayout L = ex_layout(*A, R, K);
+    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
+    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if (R.count == 0 || K.count == 0 || C->nnz == 0 || A->nnz == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    return ex_dispatch(*A, L, [&](auto ip, auto sp) {
+        return dispatch_index(C->indptr_type, [&](auto cp) {
+            auto run = [&](auto vtag) {
+                return ex_values<decltype(ip), decltype(cp), decltype(sp), decltype(vtag)>(h, *A, R, K, *C, L,
+                                                                                           ws_base(workspace));
+            };
+            switch (vbytes(A->value_type)) {   // values move as raw bits of their width
+                case 4: return run(TrBits<4>::type{});
+                case 8: return run(TrBits<8>::type{});
+                default: return run(TrBits<16>::type{});
+            }
         });
     });
 }

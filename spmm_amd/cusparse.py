@@ -60,7 +60,7 @@ def check_availability(name: str) -> bool:
     global _available
     if name not in ("spgemm", "spmv", "spmm", "validate_csr", "csr2csc", "csc2csr", "csrgeam2", "csrgeam",
                     "canonicalize", "csrsort", "csr2dense", "csc2dense", "dense2csr", "dense2csc",
-                    "denseToSparse", "sparseToDense"):
+                    "denseToSparse", "sparseToDense", "extract"):
         raise ValueError(f"No available version information specified for {name}")
     if _available is None:
         try:
@@ -776,6 +776,93 @@ def csrsort(x):
     x._canonical = None   # sorted now; canonical when it holds no duplicates
 
 
+def has_extract() -> bool:
+    """True when the loaded library exports spg_csr_extract (added within 0.2.0: an older
+    development build lacks it, and the containers then keep their torch indexing)."""
+    lib = _lib.load()
+    return hasattr(lib, "spg_csr_extract_nnz") and hasattr(lib, "spg_csr_extract")
+
+
+def _sel_view(sel):
+    """(pointer to the spg_sel_t of a selection, what keeps its memory alive): ``None`` the whole
+    axis, ``(start, step, count)`` a range, a device tensor a list."""
+    if sel is None:
+        return None, None
+    if isinstance(sel, tuple):
+        v = _lib.SpgSel(int(sel[0]), int(sel[1]), int(sel[2]), None)
+        return ctypes.byref(v), v
+    idx = sel.to(torch.int32).contiguous()
+    v = _lib.SpgSel(0, 1, int(idx.numel()), idx.data_ptr() if idx.numel() else None)
+    return ctypes.byref(v), (v, idx)
+
+
+def _extract_arrays(data, indices, indptr, shape, rows_sel, cols_sel):
+    """(data, indices, indptr) of the submatrix [rows_sel, cols_sel] of the m x n CSR arrays, on
+    spg_csr_extract_nnz + spg_csr_extract.  A selection is ``None`` (the whole axis), a range
+    ``(start, step, count)`` or a device tensor of in-range int32 indices.  The row pointer comes
+    back int32, or int64 when nnz(C) does not fit (the structure call is then repeated)."""
+    dev, dt = data.device, data.dtype
+    m, n = int(shape[0]), int(shape[1])
+    nnz = int(data.numel())
+    ipd = torch.int32 if nnz <= 2 ** 31 - 1 else torch.int64
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _lib.get_handle(idx)
+    h.set_stream(_current_stream_ptr(idx))
+    data, indices, indptr = data.contiguous(), indices.to(torch.int32).contiguous(), indptr.to(ipd).contiguous()
+    va = SpgCsr(m, n, nnz, indptr.data_ptr(), indices.data_ptr() if nnz else 0, data.data_ptr() if nnz else 0,
+                _IT[ipd], _VT[dt])
+    rp, rkeep = _sel_view(rows_sel)
+    cp, ckeep = _sel_view(cols_sel)
+    nr = m if rows_sel is None else rows_sel[2] if isinstance(rows_sel, tuple) else int(rows_sel.numel())
+    nc = n if cols_sel is None else cols_sel[2] if isinstance(cols_sel, tuple) else int(cols_sel.numel())
+    nnzc = ctypes.c_int64(0)
+    ws_bytes = ctypes.c_size_t(0)
+    check(h.lib.spg_csr_extract_nnz(h.ptr, ctypes.byref(va), rp, cp, None, _IT[torch.int32], ctypes.byref(nnzc),
+                                    ctypes.byref(ws_bytes), None), "spg_csr_extract_nnz")
+    # workspace from torch's caching allocator on the current stream, as in _spgemm
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    cpd = torch.int32
+    c_indptr = torch.empty(nr + 1, dtype=cpd, device=dev)
+    st = h.lib.spg_csr_extract_nnz(h.ptr, ctypes.byref(va), rp, cp, ctypes.c_void_p(c_indptr.data_ptr()), _IT[cpd],
+                                   ctypes.byref(nnzc), ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()))
+    if st == _lib.STATUS_OVERFLOW:   # nnz(C) past int32: the same pass into an int64 row pointer
+        cpd = torch.int64
+        c_indptr = torch.empty(nr + 1, dtype=cpd, device=dev)
+        st = h.lib.spg_csr_extract_nnz(h.ptr, ctypes.byref(va), rp, cp, ctypes.c_void_p(c_indptr.data_ptr()),
+                                       _IT[cpd], ctypes.byref(nnzc), ctypes.byref(ws_bytes),
+                                       ctypes.c_void_p(ws.data_ptr()))
+    check(st, "spg_csr_extract_nnz")
+    nz = int(nnzc.value)
+    c_indices = torch.empty(nz, dtype=torch.int32, device=dev)
+    c_data = torch.empty(nz, dtype=dt, device=dev)
+    vc = SpgCsr(nr, nc, nz, c_indptr.data_ptr(), c_indices.data_ptr() if nz else 0, c_data.data_ptr() if nz else 0,
+                _IT[cpd], _VT[dt])
+    check(h.lib.spg_csr_extract(h.ptr, ctypes.byref(va), rp, cp, ctypes.byref(vc), ws_bytes,
+                                ctypes.c_void_p(ws.data_ptr())), "spg_csr_extract")
+    del rkeep, ckeep
+    return c_data, c_indices, c_indptr
+
+
+def extract(x, rows=None, cols=None):
+    """The submatrix ``x[rows, cols]`` of a ``csr_matrix`` or ``csc_matrix`` in its own format --
+    what cupyx's ``__getitem__`` does with kernels of its own
+    (modify_src/cupy-src/cupyx/scipy/sparse/_index.py:348, :45-115; _compressed.py:403, :566, :643,
+    :665), on ``spg_csr_extract_nnz`` + ``spg_csr_extract``.  Per axis: ``None`` (everything), a
+    ``slice`` with any step, or an int sequence / array / tensor in any order, repeats allowed --
+    always one selection per axis (outer indexing), also when both are lists.  Rows keep their
+    stored entry order and values are moved bit for bit; the arrays equal scipy's array for array
+    wherever the column list has no repeat (repeats come in ascending list position)."""
+    from .sparse import _axis_selector, csc_matrix
+    if not check_availability("extract"):
+        raise RuntimeError("extract is not available.")
+    if not isinstance(x, (csr_matrix, csc_matrix)):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    if x.device.type != "cuda":
+        raise RuntimeError("extract needs device-resident operands")
+    m, n = x.shape
+    return x._extract(_axis_selector(rows, m, x.device), _axis_selector(cols, n, x.device))
+
+
 def has_dense_convert() -> bool:
     """True when the loaded library exports spg_csr2dense and spg_dense2csr (added within 0.2.0:
     an older development build lacks them, and the containers then keep their torch form)."""
@@ -1016,5 +1103,5 @@ def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float 
 
 
 __all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "csrgeam2", "csrgeam", "canonicalize", "csrsort",
-           "check_availability", "num_products", "validate_csr", "SpgError",
+           "extract", "check_availability", "num_products", "validate_csr", "SpgError",
            "last_stats"]

@@ -18,6 +18,10 @@ Mirrors the part of ``cupyx.scipy.sparse`` that the reference's hot path goes th
   _csr.py:84-96 and _csc.py:250-262): ``sum_duplicates()`` on both operands, then
   ``cusparse.csrgeam2`` (``spg_csrgeam``) for device tensors and the torch form of the same
   rule otherwise; a csc result for csc operands, through the free transposes.
+* ``A[rows, cols]`` on ``csr_matrix`` / ``csc_matrix`` (``__getitem__``, _index.py:348;
+  _compressed.py:403, :566, :643, :665): ints, slices with any step, index arrays (outer
+  indexing) and boolean masks per axis, on ``spg_csr_extract`` for device tensors and the torch
+  form of the same rule otherwise.
 
 CSR <-> CSC conversion of device tensors runs in libmi355_spgemm.so (``spg_csr2csc``, a stable
 counting sort: scipy's own order, so transposed products stay bit-exact with scipy), and so do
@@ -226,6 +230,128 @@ def _geam_torch(a: "csr_matrix", b: "csr_matrix", alpha, beta) -> "csr_matrix":
                                   _indptr_from_rows(rows, m, ipd), (m, n), canonical=True)
 
 
+def _engine_extracts(t: torch.Tensor, shape) -> bool:
+    """A[rows, cols] of these tensors runs on spg_csr_extract: they sit on a GPU, the minor
+    extent fits the engine's int32 column ids and the loaded library exports the symbols
+    (otherwise the torch form of the same rule serves)."""
+    if t.device.type != "cuda" or shape[1] > INT32_MAX:
+        return False
+    from . import cusparse
+    return cusparse.has_extract()
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _axis_selector(key, extent: int, device):
+    """One axis of an indexing key as the selection spg_csr_extract takes: ``None`` (the whole
+    axis), a range ``(start, step, count)``, or a 1-D int32 tensor of in-range indices on
+    ``device``.  Slices are normalised as Python does, negative indices wrapped, boolean masks
+    converted with ``torch.nonzero``; bounds are checked on the device with one min / max read.
+    ``IndexError`` as scipy raises it."""
+    if key is None or key is Ellipsis:
+        return None
+    if isinstance(key, slice):
+        start, stop, step = key.indices(extent)
+        count = len(range(start, stop, step))
+        if count == extent and (step == 1 or extent <= 1):
+            return None
+        return (start if count else 0, step if count > 1 else 1, count)
+    if _is_int(key):
+        i = int(key)
+        if i < -extent or i >= extent:
+            raise IndexError(f"index ({i}) out of range")
+        return (i + extent if i < 0 else i, 1, 1)
+    if isinstance(key, torch.Tensor):
+        idx = key
+    else:
+        try:
+            idx = torch.from_numpy(np.ascontiguousarray(np.asarray(key)))
+        except TypeError:
+            raise IndexError("arrays used as indices must be of integer (or boolean) type") from None
+    if idx.ndim == 2 and 1 in idx.shape and idx.dtype != torch.bool:   # an np.ix_-shaped key
+        idx = idx.reshape(-1)
+    if idx.ndim != 1:
+        raise IndexError("an index array must be one-dimensional (or np.ix_-shaped)")
+    idx = idx.to(device)
+    if idx.dtype == torch.bool:
+        if idx.numel() != extent:
+            raise IndexError(f"boolean index has {idx.numel()} entries, the axis {extent}")
+        return torch.nonzero(idx).reshape(-1).to(torch.int32)
+    if idx.numel() == 0:
+        return torch.empty(0, dtype=torch.int32, device=device)
+    if idx.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise IndexError("arrays used as indices must be of integer (or boolean) type")
+    idx = idx.to(torch.int64)
+    lo, hi = (int(v) for v in torch.aminmax(idx))
+    if lo < -extent or hi >= extent:
+        raise IndexError(f"index ({lo if lo < -extent else hi}) out of range")
+    if lo < 0:
+        idx = torch.where(idx < 0, idx + extent, idx)
+    return idx.to(torch.int32).contiguous()
+
+
+def _selector_count(sel, extent: int) -> int:
+    return extent if sel is None else sel[2] if isinstance(sel, tuple) else int(sel.numel())
+
+
+def _extract_torch(data, indices, indptr, n_major: int, n_minor: int, major_sel, minor_sel):
+    """(data, indices, indptr) of the submatrix as torch ops -- spg_csr_extract's rule
+    (include/spgemm.h): output segment i is source segment sel(i) in stored order; an entry with
+    minor index j stays as j (the whole axis), becomes (j - start) / step where the range holds it,
+    or one entry per position of j in the list, positions ascending (a stable sort of the list)."""
+    dev = data.device
+    ip = indptr.to(torch.int64)
+    if major_sel is None:
+        r = torch.arange(n_major, device=dev)
+    elif isinstance(major_sel, tuple):
+        r = major_sel[0] + major_sel[1] * torch.arange(major_sel[2], device=dev)
+    else:
+        r = major_sel.to(torch.int64)
+    nr = int(r.numel())
+    starts = ip[r]
+    lens = ip[r + 1] - starts
+    seg = torch.repeat_interleave(torch.arange(nr, device=dev), lens)
+    first = torch.cumsum(lens, 0) - lens
+    e = starts[seg] + (torch.arange(seg.numel(), device=dev) - first[seg])
+    j = indices[e].to(torch.int64)
+    if minor_sel is None:
+        minor = j
+    elif isinstance(minor_sel, tuple):
+        start, step, count = minor_sel
+        d = j - start
+        t = torch.div(d, step, rounding_mode="trunc")
+        ok = (t * step == d) & (t >= 0) & (t < count)
+        e, seg, minor = e[ok], seg[ok], t[ok]
+    else:
+        idx = minor_sel.to(torch.int64)
+        _, colpos = torch.sort(idx, stable=True)   # positions grouped by listed index, ascending inside one
+        colptr = torch.zeros(n_minor + 1, dtype=torch.int64, device=dev)
+        if idx.numel():
+            colptr[1:] = torch.cumsum(torch.bincount(idx, minlength=n_minor), 0)
+        mult = colptr[j + 1] - colptr[j]
+        src = torch.repeat_interleave(torch.arange(j.numel(), device=dev), mult)
+        u = torch.arange(src.numel(), device=dev) - (torch.cumsum(mult, 0) - mult)[src]
+        minor = colpos[colptr[j[src]] + u]
+        e, seg = e[src], seg[src]
+    ipd = torch.int32 if e.numel() <= INT32_MAX else torch.int64
+    return data[e].contiguous(), minor.to(torch.int32), _indptr_from_rows(seg, nr, ipd)
+
+
+def _extract_compressed(data, indices, indptr, n_major: int, n_minor: int, major_sel, minor_sel, canonical):
+    """The selected major segments and minor indices of compressed arrays, with the canonical
+    flag of the result: the source's when the minor axis is kept or cut by an ascending range,
+    unknown (``None``: checked lazily) for a list or a descending range."""
+    if _engine_extracts(data, (n_major, n_minor)):
+        from . import cusparse
+        parts = cusparse._extract_arrays(data, indices, indptr, (n_major, n_minor), major_sel, minor_sel)
+    else:
+        parts = _extract_torch(data, indices, indptr, n_major, n_minor, major_sel, minor_sel)
+    keeps = minor_sel is None or (isinstance(minor_sel, tuple) and minor_sel[1] > 0)
+    return parts, (canonical if keeps else None)
+
+
 def isspmatrix(x) -> bool:
     return isinstance(x, _SparseBase)
 
@@ -318,6 +444,64 @@ class _Compressed(_SparseBase):
         """Elementwise negative over the same structure (cupyx _data.py:36-38)."""
         out = self.copy()
         out.data = _negated(self.data)
+        return out
+
+    # ------------------------------------------------------------------ indexing
+    def _extract(self, rows_sel, cols_sel):
+        """self[rows, cols] for two selections of ``_axis_selector``'s kind, in this format: a CSC
+        matrix is the same extraction on its arrays with the selections swapped."""
+        m, n = self._shape
+        if rows_sel is None and cols_sel is None:
+            return self.copy()
+        csr = self.format == "csr"
+        n_major, n_minor = (m, n) if csr else (n, m)
+        major, minor = (rows_sel, cols_sel) if csr else (cols_sel, rows_sel)
+        (data, indices, indptr), canon = _extract_compressed(self.data, self.indices, self.indptr, n_major, n_minor,
+                                                              major, minor, self._canonical)
+        shape = (_selector_count(rows_sel, m), _selector_count(cols_sel, n))
+        if csr:
+            return csr_matrix._from_parts(data, indices, indptr, shape, canonical=canon)
+        return csc_matrix((data, indices, indptr), shape=shape, canonical=canon)
+
+    def __getitem__(self, key):
+        """``A[rows, cols]`` as scipy gives it (cupyx _index.py:348): per axis an int, a slice with
+        any step, an integer sequence / array / tensor (negative entries wrapped, any order,
+        repeats allowed) or a boolean mask.  Index arrays are read as OUTER indexing, one per axis:
+        ``A[rows][:, cols]``, ``A[np.ix_(rows, cols)]``-shaped keys and ``A[rows, c0:c1]`` name the
+        same submatrix.  An int gives a 1 x n or m x 1 matrix, ``A[i, j]`` the element (the sum of
+        its stored duplicates) as a Python scalar, ``A[:]`` a copy.  Two 1-D index arrays at once
+        are scipy's inner (pointwise) indexing, a different operation with a dense result:
+        ``NotImplementedError``.  spg_csr_extract for device tensors, else the torch form of the
+        same rule."""
+        if not isinstance(key, tuple):
+            key = (key, slice(None))
+        elif len(key) == 1:
+            key = (key[0], slice(None))
+        elif len(key) != 2:
+            raise IndexError("a sparse matrix takes at most two indices")
+
+        def scalar(k):   # 0-d arrays and tensors index like ints
+            if isinstance(k, (np.ndarray, torch.Tensor)) and k.ndim == 0 and k.dtype not in (np.bool_, torch.bool):
+                return int(k)
+            return k
+
+        rk, ck = scalar(key[0]), scalar(key[1])
+
+        def array_ndim(k):
+            if isinstance(k, (slice, type(None), type(Ellipsis))) or _is_int(k):
+                return None
+            return k.ndim if isinstance(k, (np.ndarray, torch.Tensor)) else np.ndim(k)
+
+        if array_ndim(rk) == 1 and array_ndim(ck) == 1:
+            if len(rk) != len(ck):
+                raise IndexError("shape mismatch: the two index arrays do not broadcast")
+            raise NotImplementedError(
+                "two index arrays select elements pointwise (scipy's inner indexing), which gives a dense "
+                "vector and is another operation; for the submatrix use A[rows][:, cols] or np.ix_(rows, cols)")
+        m, n = self._shape
+        out = self._extract(_axis_selector(rk, m, self.device), _axis_selector(ck, n, self.device))
+        if _is_int(rk) and _is_int(ck):   # (scipy's _get_intXint: duplicates summed)
+            return out.data.sum().item()
         return out
 
 
