@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "spgemm.h"
+#include "spg_format_layouts.hpp"
 #include "spgemm_kernels.hpp"
 #include "spgemm_tile.hpp"
 #include "spgemm_tile_dn.hpp"
@@ -29,6 +30,7 @@
 #include "spgemm_canon.hpp"
 #include "spgemm_extract.hpp"
 #include "spgemm_dense.hpp"
+#include "spgemm_cols16.hpp"
 
 using namespace spg;
 
@@ -144,12 +146,6 @@ struct spg_plan_s {
 // ----------------------------------------------------------------------------- helpers
 namespace {
 
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-inline size_t vbytes(spg_dtype_t t) {
-    return t == SPG_C_64F ? 16 : (t == SPG_R_64F || t == SPG_C_32F) ? 8 : 4;
-}
-
 // bytes of one tile-major B record of the tile path (column in tile + value, unpadded)
 inline size_t brec_bytes(spg_dtype_t t) {
     return t == SPG_R_64F ? 10 : t == SPG_R_32F ? 6 : 4 + vbytes(t);   // (rec_bytes, spgemm_tile.hpp)
@@ -182,18 +178,6 @@ template <typename F>
 spg_status_t dispatch_index(spg_index_t ip, spg_index_t cp, F&& f) {
     return dispatch_index(ip, [&](auto i) { return dispatch_index(cp, [&](auto c) { return f(i, c); }); });
 }
-inline size_t index_bytes(spg_index_t t) { return t == SPG_INDEX_64I ? 8 : 4; }
-
-// Workspace carving.  A cursor over offsets from the workspace's base: take(bytes) returns the
-// current offset and advances to the next 256-byte boundary.
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes);
-        return at;
-    }
-};
 // the 256-byte aligned base of a caller's workspace (the newer entry points ask for 256 bytes
 // of slack instead of an aligned pointer)
 inline char* ws_base(void* workspace) { return (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
@@ -216,11 +200,6 @@ inline bool row_kernel_enabled() {
     return on;
 }
 
-inline int64_t grid_for(int64_t rows, int per_block) { return (rows + per_block - 1) / per_block; }
-
-inline int64_t scan_tiles(int64_t n) { return n > 0 ? (n + SCAN_TILE - 1) / SCAN_TILE : 1; }
-// bytes of the status words of a look-back scan over n elements: a ticket + one word per tile
-inline size_t status_bytes(int64_t n) { return sizeof(unsigned long long) * (size_t)(scan_tiles(n) + 1); }
 // 64-row groups (ALG1 on k_row: one published prefix per group)
 inline int64_t row_groups(int64_t n) { return (n + WAVE - 1) / WAVE; }
 
@@ -1661,38 +1640,91 @@ spg_status_t spmm_launch(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& 
     return SPG_STATUS_SUCCESS;
 }
 
-// ----------------------------------------------------------------------------- spg_csr2csc
+// ----------------------------------------------------------------------------- format operations: shared pieces
+// (spg_csr2csc ... spg_csr_extract below; their workspace carves: spg_format_layouts.hpp)
 
-// Workspace carve of spg_csr2csc (offsets from the 256-byte aligned base).
-struct TrLayout {
-    int passes = 1;            // 8-bit digit passes: the bytes of cols - 1 (at least one)
-    int64_t chunks = 0;        // wave chunks of TR_CHUNK entries
-    int nbuf = 0;              // ping-pong record buffers the passes need (0, 1 or 2)
-    size_t scalars = 0, status = 0, table = 0, skeys = 0, buf[2] = {0, 0};
-    size_t keys = 0, rowids = 0, pos = 0;   // inside one record buffer
-    size_t total = 0;          // bytes to ask for (256 of slack for the base alignment)
-};
-
-TrLayout tr_layout(const spg_csr_t& A) {
-    TrLayout L;
-    const size_t ips = index_bytes(A.indptr_type);
-    const uint64_t top = A.cols > 0 ? (uint64_t)(A.cols - 1) : 0;
-    L.passes = top >= (1ull << 24) ? 4 : top >= (1ull << 16) ? 3 : top >= (1ull << 8) ? 2 : 1;
-    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
-    L.nbuf = std::min(L.passes - 1, 2);
-    Carver c;
-    L.scalars = c.take(16 * sizeof(int64_t));
-    L.status = c.take(status_bytes(TR_RADIX * L.chunks));
-    L.table = c.take(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
-    L.skeys = c.take(sizeof(int32_t) * (size_t)A.nnz);   // the sorted columns (the last pass -> k_tr_indptr)
-    Carver rec;   // one record buffer: keys | row ids | positions
-    L.keys = rec.take(sizeof(int32_t) * (size_t)A.nnz);
-    L.rowids = rec.take(sizeof(int32_t) * (size_t)A.nnz);
-    L.pos = rec.take(ips * (size_t)A.nnz);
-    for (int b = 0; b < L.nbuf; ++b) L.buf[b] = c.take(rec.off);
-    L.total = c.off + 256;
-    return L;
+// f(V{}) with V the raw bits of value type t's width: for the kernels that only move values
+template <typename F>
+spg_status_t dispatch_bits(spg_dtype_t t, F&& f) {
+    switch (vbytes(t)) {
+        case 4: return f(TrBits<4>::type{});
+        case 8: return f(TrBits<8>::type{});
+        default: return f(TrBits<16>::type{});
+    }
 }
+
+// blocks of a kernel whose threads stride over n items, `block` of them per block
+inline unsigned strided_grid(int64_t n, int block) { return (unsigned)std::min<int64_t>(grid_for(n, block), 1 << 20); }
+
+// The tail of a structure call: the last scan's total into *nnzC, OVERFLOW when the scan flagged it.
+spg_status_t scan_total(spg_handle_t h, const int64_t* scal, int64_t* nnzC) {
+    int64_t sc[2] = {0, 0};
+    const spg_status_t st = read_scalars(h, scal, 2, sc);
+    if (st) return st;
+    *nnzC = sc[0];
+    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+}
+
+// The passes of the least-significant-digit radix sort (spgemm_transpose.hpp) over n records in
+// `chunks` wave chunks, digits of 8 bits from `shift0` up.  A pass is k_tr_hist into the digit
+// table, the scan of the table in place, and the caller's scatter: keys_of(p) is the KS functor
+// over pass p's input, scatter(p, shift) launches pass p's scatter.
+template <typename IP, typename KeysOf, typename Scatter>
+spg_status_t sort_passes(spg_handle_t h, int64_t n, int64_t chunks, int passes, int shift0, IP* table,
+                         unsigned long long* status, int64_t* scal, KeysOf&& keys_of, Scatter&& scatter) {
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    for (int p = 0; p < passes; ++p) {
+        const int shift = shift0 + 8 * p;
+        auto keys = keys_of(p);
+        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP, decltype(keys)>, grid, block, n, chunks, keys, shift, table);
+        SPG_LAUNCHED(h);
+        const spg_status_t st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true);
+        if (st) return st;
+        scatter(p, shift);
+        SPG_LAUNCHED(h);
+    }
+    return SPG_STATUS_SUCCESS;
+}
+
+// The sort of (key, position) records between the two ping-pong buffers `buf`: sort_passes with
+// k_cn_scatter.  The caller packs buf[0], every pass moves the records to the other buffer, and
+// the sorted ones are in buf[sorted_buf(passes)] -- for the value calls too.
+inline int sorted_buf(int passes) { return passes & 1; }
+template <typename IP, typename K>
+spg_status_t sort_records(spg_handle_t h, int64_t n, int64_t chunks, int passes, int shift0, CnRec<IP, K>* const buf[2],
+                          IP* table, unsigned long long* status, int64_t* scal) {
+    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    return sort_passes(
+        h, n, chunks, passes, shift0, table, status, scal, [&](int p) { return CnKeys<IP, K>{buf[p & 1], 0}; },
+        [&](int p, int shift) {
+            timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<IP, K>, grid, block, n, chunks, shift,
+                         (const CnRec<IP, K>*)buf[p & 1], (const IP*)table, buf[(p + 1) & 1]);
+        });
+}
+
+// the two row-pointer types a result may have
+inline spg_status_t check_index_type(spg_index_t t) {
+    return t == SPG_INDEX_32I || t == SPG_INDEX_64I ? SPG_STATUS_SUCCESS : SPG_STATUS_INVALID_VALUE;
+}
+
+// What a value call asks of its result C and its workspace: the shape and value type the structure
+// call answered for, an entry count, a row-pointer type, `total` bytes, and then C's arrays.
+inline spg_status_t check_result(const spg_csr_t* C, int64_t rows, int64_t cols, spg_dtype_t value_type,
+                                 size_t workspace_bytes, size_t total) {
+    if (C->rows != rows || C->cols != cols || C->value_type != value_type || C->nnz < 0) return SPG_STATUS_INVALID_VALUE;
+    if (check_index_type(C->indptr_type) || workspace_bytes < total) return SPG_STATUS_INVALID_VALUE;
+    return !C->indptr || (C->nnz > 0 && (!C->indices || !C->values)) ? SPG_STATUS_INVALID_VALUE : SPG_STATUS_SUCCESS;
+}
+
+// A structure call's answer for an empty result: a row pointer of `entries` zeros and, where the
+// call reports one, *nnzC = 0.
+spg_status_t empty_structure(spg_handle_t h, void* C_indptr, spg_index_t type, int64_t entries, int64_t* nnzC) {
+    SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(type) * (size_t)entries, h->stream));
+    if (nnzC) *nnzC = 0;
+    return SPG_STATUS_SUCCESS;
+}
+
+// ----------------------------------------------------------------------------- spg_csr2csc
 
 template <typename IP>
 spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrLayout& L, char* ws) {
@@ -1702,87 +1734,46 @@ spg_status_t tr_run(spg_handle_t h, const spg_csr_t& A, spg_csr_t& AT, const TrL
     IP* table = (IP*)(ws + L.table);
     IP* ATp = (IP*)AT.indptr;
     const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    // the records a pass reads: A's entries themselves, then what the pass before it wrote
     const int32_t* kin = (const int32_t*)A.indices;
     const int32_t* rin = nullptr;
     const IP* pin = nullptr;
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    for (int p = 0; p < L.passes; ++p) {
-        const int shift = 8 * p;
-        const bool first = p == 0, last = p == L.passes - 1;
-        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP>, grid, block, nnz, chunks, TrKeys{kin}, shift, table);
-        SPG_LAUNCHED(h);
-        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
+    auto scatter = [&](int p, int shift) {
+        const bool last = p == L.passes - 1;
         char* out = last ? nullptr : ws + L.buf[p & 1];
         int32_t* kout = last ? (int32_t*)(ws + L.skeys) : (int32_t*)(out + L.keys);
         int32_t* rout = last ? nullptr : (int32_t*)(out + L.rowids);
         IP* pout = last ? nullptr : (IP*)(out + L.pos);
-        if (!last) {
-            using V = uint32_t;   // (no value is touched before the last pass)
-            if (first)
-                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, false>, grid, block, nnz, chunks, shift,
-                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
-                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
-            else
-                timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, false>, grid, block, nnz, chunks, shift,
-                             kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
-                             (const V*)nullptr, (int32_t*)nullptr, (V*)nullptr);
-        } else {
-            auto run_last = [&](auto vtag) {
-                using V = decltype(vtag);
-                if (first)
-                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, true, true>, grid, block, nnz, chunks,
-                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
-                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
-                else
-                    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, false, true>, grid, block, nnz, chunks,
-                                 shift, kin, rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout,
-                                 pout, (const V*)A.values, (int32_t*)AT.indices, (V*)AT.values);
-            };
-            switch (vbytes(A.value_type)) {
-                case 4: run_last(TrBits<4>::type{}); break;
-                case 8: run_last(TrBits<8>::type{}); break;
-                default: run_last(TrBits<16>::type{}); break;
-            }
-        }
-        SPG_LAUNCHED(h);
+        // the one launch: V the values' raw bits, FIRST / LAST the kernel's template flags as tags
+        auto launch = [&](auto vtag, auto first_tag, auto last_tag) {
+            using V = decltype(vtag);
+            constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
+            timed_launch(h, SPG_PHASE_LAYOUT, k_tr_scatter<IP, V, FIRST, LAST>, grid, block, nnz, chunks, shift, kin,
+                         rin, pin, (const IP*)A.indptr, A.rows, (const IP*)table, kout, rout, pout,
+                         LAST ? (const V*)A.values : nullptr, LAST ? (int32_t*)AT.indices : nullptr,
+                         LAST ? (V*)AT.values : nullptr);
+            return SPG_STATUS_SUCCESS;
+        };
+        auto by_first = [&](auto vtag, auto last_tag) {
+            return p == 0 ? launch(vtag, std::true_type{}, last_tag) : launch(vtag, std::false_type{}, last_tag);
+        };
+        if (last) dispatch_bits(A.value_type, [&](auto vtag) { return by_first(vtag, std::true_type{}); });
+        else by_first(uint32_t{}, std::false_type{});   // (no value is touched before the last pass)
         kin = kout;
         rin = rout;
         pin = pout;
-    }
+    };
+    const spg_status_t st = sort_passes(h, nnz, chunks, L.passes, 0, table, status, scal,
+                                        [&](int) { return TrKeys{kin}; }, scatter);
+    if (st) return st;
     // (kin: the sorted columns the last pass left)
-    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP, IP>, dim3(pgrid), dim3(256), nnz, A.cols, TrKeys{kin}, ATp,
-                 (const IP*)nullptr);
+    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<IP, IP>, dim3(strided_grid(A.cols + 1, 256)), dim3(256), nnz, A.cols,
+                 TrKeys{kin}, ATp, (const IP*)nullptr);
     SPG_LAUNCHED(h);
     return SPG_STATUS_SUCCESS;
 }
 
 // ----------------------------------------------------------------------------- spg_csrgeam
-
-// Workspace carve of spg_csrgeam_nnz / spg_csrgeam (offsets from the 256-byte aligned base).
-struct GmLayout {
-    int64_t chunksA = 0, chunksB = 0;   // wave chunks of GM_CHUNK entries
-    size_t scalars = 0;                 // 16 int64: [0] a scan's total, [1] its overflow flag
-    size_t status_b = 0, status_r = 0;  // look-back words of the scan over B's entries / over the rows
-    size_t S = 0;                       // nnz(B) + 1 IP: B-only marks, scanned in place (kept for the value pass)
-    size_t cnt = 0;                     // rows + 1 int64: entries per row of C
-    size_t total = 0;                   // bytes to ask for (256 of slack for the base alignment)
-};
-
-GmLayout gm_layout(const spg_csr_t& A, const spg_csr_t& B) {
-    GmLayout L;
-    const size_t ips = index_bytes(A.indptr_type);
-    L.chunksA = (A.nnz + GM_CHUNK - 1) / GM_CHUNK;
-    L.chunksB = (B.nnz + GM_CHUNK - 1) / GM_CHUNK;
-    Carver c;
-    L.scalars = c.take(16 * sizeof(int64_t));
-    L.status_b = c.take(status_bytes(B.nnz));
-    L.status_r = c.take(status_bytes(A.rows));
-    L.S = c.take(ips * ((size_t)B.nnz + 1));
-    L.cnt = c.take(sizeof(int64_t) * ((size_t)A.rows + 1));
-    L.total = c.off + 256;
-    return L;
-}
 
 // what both entry points ask of the operands
 spg_status_t gm_check(const spg_csr_t* A, const spg_csr_t* B) {
@@ -1809,16 +1800,12 @@ spg_status_t gm_structure(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B
         SPG_LAUNCHED(h);
     }
     if ((st = launch_scan<IP, IP>(h, B.nnz, S, S, (unsigned long long*)(ws + L.status_b), scal, true))) return st;
-    const unsigned cgrid = (unsigned)std::min<int64_t>(grid_for(A.rows, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_count<IP>, dim3(cgrid), dim3(256), A.rows, (const IP*)A.indptr,
-                 (const IP*)B.indptr, (const IP*)S, cnt);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_geam_count<IP>, dim3(strided_grid(A.rows, 256)), dim3(256), A.rows,
+                 (const IP*)A.indptr, (const IP*)B.indptr, (const IP*)S, cnt);
     SPG_LAUNCHED(h);
     if ((st = launch_scan<CP, int64_t>(h, A.rows, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
         return st;
-    int64_t sc[2] = {0, 0};
-    if ((st = read_scalars(h, scal, 2, sc))) return st;
-    *nnzC = sc[0];
-    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+    return scan_total(h, scal, nnzC);
 }
 
 template <typename IP, typename CP, typename T>
@@ -1874,30 +1861,6 @@ spg_status_t dn_todense(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& D
     return SPG_STATUS_SUCCESS;
 }
 
-// Workspace carve of spg_dense2csr_nnz / spg_dense2csr (offsets from the 256-byte aligned base).
-struct DnLayout {
-    int64_t nseg = 1;        // segments of DV_S columns per row
-    int64_t entries = 0;     // rows * nseg: the (row, segment) table
-    int64_t tasks = 0;       // wave tasks (row-major) or workgroup tasks (column-major)
-    size_t scalars = 0;      // 16 int64: [0] the scan's total, [1] its overflow flag
-    size_t status = 0;       // look-back words of the scan over the table
-    size_t table = 0;        // entries + 1 positions (8 bytes each, whatever C's row-pointer type)
-    size_t total = 0;        // bytes to ask for (256 of slack for the base alignment)
-};
-
-DnLayout dn_layout(const spg_dense_t& D) {
-    DnLayout L;
-    L.nseg = std::max<int64_t>(1, grid_for(D.cols, DV_S));
-    L.entries = D.rows * L.nseg;
-    L.tasks = D.order == SPG_ORDER_COL ? grid_for(D.rows, DV_T) * L.nseg : L.entries;
-    Carver c;
-    L.scalars = c.take(16 * sizeof(int64_t));
-    L.status = c.take(status_bytes(L.entries));
-    L.table = c.take(sizeof(int64_t) * ((size_t)L.entries + 1));
-    L.total = c.off + 256;
-    return L;
-}
-
 // f(kernel-selecting tags): E elements per lane and step, COL the order
 template <typename T, typename F>
 void dn_dispatch_read(const spg_dense_t& D, F&& f) {
@@ -1923,13 +1886,10 @@ spg_status_t dn_structure(spg_handle_t h, const spg_dense_t& D, const DnLayout& 
     spg_status_t st = SPG_STATUS_SUCCESS;
     if ((st = launch_scan<CP, CP>(h, L.entries, table, table, (unsigned long long*)(ws + L.status), scal, true)))
         return st;
-    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(D.rows + 1, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_SYMBOLIC, k_dn_indptr<CP>, dim3(pgrid), dim3(256), D.rows, L.nseg, (const CP*)table, Cp);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_dn_indptr<CP>, dim3(strided_grid(D.rows + 1, 256)), dim3(256), D.rows, L.nseg,
+                 (const CP*)table, Cp);
     SPG_LAUNCHED(h);
-    int64_t sc[2] = {0, 0};
-    if ((st = read_scalars(h, scal, 2, sc))) return st;
-    *nnzC = sc[0];
-    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+    return scan_total(h, scal, nnzC);
 }
 
 template <typename T, typename CP>
@@ -1947,62 +1907,6 @@ spg_status_t dn_values(spg_handle_t h, const spg_dense_t& D, spg_csr_t& C, const
 }
 
 // ----------------------------------------------------------------------------- spg_canonicalize
-
-// bits of an index below `extent`: the bits of extent - 1 (at least one)
-inline int index_bits(int64_t extent) {
-    int b = 1;
-    while (b < 63 && ((int64_t)1 << b) < extent) ++b;
-    return b;
-}
-
-// Workspace carve of spg_canonicalize_nnz / spg_canonicalize (offsets from the 256-byte aligned
-// base).  The sorted records stay in buf[passes & 1] and the scanned marks in `kept` for the
-// value call.
-struct CnLayout {
-    bool sum = false, drop = false;
-    bool marks = false;         // SUM or DROP_ZEROS: kept[] exists
-    int cbits = 1, rbits = 1;   // key = row << cbits | column
-    bool k64 = false;           // the key takes 64 bits
-    int shift0 = 0;             // the first digit's shift: 0, or cbits when only the rows are sorted (COO, no op)
-    int passes = 0;             // 0: CSR input with DROP_ZEROS alone, no sort (the entries are their own records)
-    int64_t chunks = 0;         // wave chunks of TR_CHUNK entries
-    size_t scalars = 0;         // 16 int64: [0] a scan's total
-    size_t status_t = 0, status_k = 0;   // look-back words of the table scans / of the scan over kept[]
-    size_t table = 0;           // 256 * chunks + 1 IP: a pass's digit histogram, scanned in place
-    size_t kept = 0;            // nnz + 1 IP: the kept marks, scanned in place
-    size_t buf[2] = {0, 0};     // ping-pong record buffers (k_cn_pack writes buf[0])
-    size_t total = 0;           // bytes to ask for (256 of slack for the base alignment)
-};
-
-CnLayout cn_layout(const spg_csr_t& A, bool coo, unsigned ops) {
-    CnLayout L;
-    const size_t ips = index_bytes(A.indptr_type);
-    const size_t nnz = (size_t)A.nnz;
-    L.sum = (ops & SPG_CANON_SUM) != 0;
-    L.drop = (ops & SPG_CANON_DROP_ZEROS) != 0;
-    L.marks = L.sum || L.drop;
-    const bool sort = L.sum || (ops & SPG_CANON_SORT) != 0;
-    L.cbits = index_bits(A.cols);
-    L.rbits = index_bits(A.rows);
-    L.k64 = L.cbits + L.rbits > 32;
-    L.shift0 = sort ? 0 : L.cbits;
-    L.passes = sort || coo ? (L.cbits + L.rbits - L.shift0 + 7) / 8 : 0;
-    L.chunks = (A.nnz + TR_CHUNK - 1) / TR_CHUNK;
-    Carver c;
-    L.scalars = c.take(16 * sizeof(int64_t));
-    if (L.passes) {
-        L.status_t = c.take(status_bytes(TR_RADIX * L.chunks));
-        L.table = c.take(ips * ((size_t)TR_RADIX * (size_t)L.chunks + 1));   // (+ 1: the scan writes its total)
-    }
-    if (L.marks) {
-        L.status_k = c.take(status_bytes(A.nnz));
-        L.kept = c.take(ips * (nnz + 1));
-    }
-    const size_t rec = (ips == 4 && !L.k64 ? 8 : 16) * nnz;   // sizeof(CnRec<IP, K>) each
-    for (int b = 0; b < (L.passes ? 2 : 0); ++b) L.buf[b] = c.take(rec);
-    L.total = c.off + 256;
-    return L;
-}
 
 // what both entry points ask of the input
 spg_status_t cn_check(const spg_csr_t* A, const int32_t* coo_rows, unsigned ops) {
@@ -2024,7 +1928,7 @@ spg_status_t cn_check(const spg_csr_t* A, const int32_t* coo_rows, unsigned ops)
 // the sorted records the structure call left (nullptr: unsorted, A's entries themselves)
 template <typename IP, typename K>
 const CnRec<IP, K>* cn_records(const CnLayout& L, char* ws) {
-    return L.passes ? (const CnRec<IP, K>*)(ws + L.buf[L.passes & 1]) : nullptr;
+    return L.passes ? (const CnRec<IP, K>*)(ws + L.buf[sorted_buf(L.passes)]) : nullptr;
 }
 
 template <typename IP, typename K>
@@ -2032,27 +1936,13 @@ spg_status_t cn_sort(spg_handle_t h, const spg_csr_t& A, const int32_t* coo_rows
     using Rec = CnRec<IP, K>;
     static_assert(sizeof(Rec) == (sizeof(IP) + sizeof(K) == 8 ? 8 : 16), "cn_layout's record size");
     const int64_t nnz = A.nnz, chunks = L.chunks;
-    int64_t* scal = (int64_t*)(ws + L.scalars);
-    unsigned long long* status = (unsigned long long*)(ws + L.status_t);
-    IP* table = (IP*)(ws + L.table);
-    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
+    Rec* const buf[2] = {(Rec*)(ws + L.buf[0]), (Rec*)(ws + L.buf[1])};
     auto pack = coo_rows ? k_cn_pack<IP, K, CN_FROM_COO> : k_cn_pack<IP, K, CN_FROM_CSR>;
-    timed_launch(h, SPG_PHASE_LAYOUT, pack, grid, block, nnz, chunks, L.cbits, (const int32_t*)A.indices, coo_rows,
-                 (const IP*)A.indptr, A.rows, (Rec*)(ws + L.buf[0]));
+    timed_launch(h, SPG_PHASE_LAYOUT, pack, dim3((unsigned)grid_for(chunks, TR_WPB)), dim3(TR_WPB * WAVE), nnz, chunks,
+                 L.cbits, (const int32_t*)A.indices, coo_rows, (const IP*)A.indptr, A.rows, buf[0]);
     SPG_LAUNCHED(h);
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    for (int p = 0; p < L.passes; ++p) {
-        const int shift = L.shift0 + 8 * p;
-        const Rec* in = (const Rec*)(ws + L.buf[p & 1]);
-        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<IP, CnKeys<IP, K>>, grid, block, nnz, chunks,
-                     CnKeys<IP, K>{in, 0}, shift, table);
-        SPG_LAUNCHED(h);
-        if ((st = launch_scan<IP, IP>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<IP, K>, grid, block, nnz, chunks, shift, in,
-                     (const IP*)table, (Rec*)(ws + L.buf[(p + 1) & 1]));
-        SPG_LAUNCHED(h);
-    }
-    return SPG_STATUS_SUCCESS;
+    return sort_records<IP, K>(h, nnz, chunks, L.passes, L.shift0, buf, (IP*)(ws + L.table),
+                               (unsigned long long*)(ws + L.status_t), (int64_t*)(ws + L.scalars));
 }
 
 template <typename IP, typename CP, typename K>
@@ -2083,9 +1973,8 @@ spg_status_t cn_structure(spg_handle_t h, const spg_csr_t& A, const int32_t* coo
             return st;
     }
     if (L.passes) {   // off the sorted keys' rows
-        const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.rows + 1, 256), 1 << 20);
-        timed_launch(h, SPG_PHASE_SYMBOLIC, k_tr_indptr<IP, CP, CnKeys<IP, K>>, dim3(pgrid), dim3(256), nnz, A.rows,
-                     CnKeys<IP, K>{rec, L.cbits}, Cp, (const IP*)kept);
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_tr_indptr<IP, CP, CnKeys<IP, K>>, dim3(strided_grid(A.rows + 1, 256)),
+                     dim3(256), nnz, A.rows, CnKeys<IP, K>{rec, L.cbits}, Cp, (const IP*)kept);
     } else {
         timed_launch(h, SPG_PHASE_SYMBOLIC, k_cn_indptr<IP, CP>, dim3((unsigned)grid_for(A.rows + 1, CN_BLOCK)),
                      dim3(CN_BLOCK), A.rows, (const IP*)A.indptr, (const IP*)kept, Cp);
@@ -2119,124 +2008,35 @@ spg_status_t cn_dispatch(const spg_csr_t& A, const CnLayout& L, F&& f) {
 
 // ----------------------------------------------------------------------------- spg_csr_extract
 
-// One axis' selection after the host checks: a NULL spg_sel_t is the whole axis, a range of at
-// most one member has step 1.
-struct ExSel {
-    bool whole = true;
-    int64_t start = 0, step = 1, count = 0;
-    const int32_t* index = nullptr;
-};
-
-// `sel` over an axis of `extent` members, checked on the host (list entries are not read).
-spg_status_t ex_sel(const spg_sel_t* sel, int64_t extent, ExSel& out) {
-    out = ExSel{};
-    out.count = extent;
-    if (!sel) return SPG_STATUS_SUCCESS;
-    out.whole = false;
-    out.count = sel->count;
-    out.index = sel->index;
-    if (sel->count < 0) return SPG_STATUS_INVALID_VALUE;
-    if (sel->count > 2147483647LL) return SPG_STATUS_NOT_SUPPORTED;
-    if (sel->index) return SPG_STATUS_SUCCESS;
-    if (sel->count > 1 && sel->step == 0) return SPG_STATUS_INVALID_VALUE;
-    out.start = sel->start;
-    out.step = sel->count > 1 ? sel->step : 1;
-    if (sel->count > 0) {
-        const __int128 last = (__int128)out.start + (__int128)(out.count - 1) * out.step;
-        if (out.start < 0 || out.start >= extent || last < 0 || last >= extent) return SPG_STATUS_INVALID_VALUE;
-    }
-    return SPG_STATUS_SUCCESS;
-}
-
-// Workspace carve of spg_csr_extract_nnz / spg_csr_extract (offsets from the 256-byte aligned
-// base).  S, and with a column list colptr and the sorted records, stay for the value call.
-struct ExLayout {
-    int kmode = EX_ALL;
-    bool s64 = false;           // S is int64 (a column list, or A's row pointer is)
-    bool contig = false;        // K = all over a step-1 row range: one span of A
-    int passes = 0;             // sort passes over the listed columns' bits
-    int64_t kchunks = 0;        // wave chunks of TR_CHUNK list positions
-    size_t scalars = 0;         // 16 int64: [0] a scan's total, [1] its overflow flag
-    size_t status_e = 0, status_r = 0, status_t = 0;   // look-back words: over A's entries / the output rows / the sort's table
-    size_t S = 0;               // nnz(A) + 1 SP: mult, scanned in place
-    size_t cnt = 0;             // nr + 1 int64: entries per output row
-    size_t table = 0;           // 256 * kchunks + 1 int32: a pass's digit histogram, scanned in place
-    size_t colptr = 0;          // cols + 1 int32
-    size_t buf[2] = {0, 0};     // ping-pong records of the list (k_ex_pack writes buf[0])
-    size_t total = 0;           // bytes to ask for (256 of slack for the base alignment)
-};
-
-ExLayout ex_layout(const spg_csr_t& A, const ExSel& R, const ExSel& K) {
-    ExLayout L;
-    L.kmode = K.whole ? EX_ALL : K.index ? EX_LIST : EX_RANGE;
-    L.s64 = L.kmode == EX_LIST || A.indptr_type == SPG_INDEX_64I;
-    L.contig = L.kmode == EX_ALL && !R.index && R.step == 1;
-    Carver c;
-    L.scalars = c.take(16 * sizeof(int64_t));
-    L.status_r = c.take(status_bytes(R.count));
-    L.cnt = c.take(sizeof(int64_t) * ((size_t)R.count + 1));
-    if (L.kmode != EX_ALL) {
-        L.status_e = c.take(status_bytes(A.nnz));
-        L.S = c.take((L.s64 ? 8 : 4) * ((size_t)A.nnz + 1));
-    }
-    if (L.kmode == EX_LIST) {
-        L.passes = (index_bits(A.cols) + 7) / 8;
-        L.kchunks = (K.count + TR_CHUNK - 1) / TR_CHUNK;
-        L.status_t = c.take(status_bytes(TR_RADIX * L.kchunks));
-        L.table = c.take(sizeof(int32_t) * ((size_t)TR_RADIX * (size_t)L.kchunks + 1));
-        L.colptr = c.take(sizeof(int32_t) * ((size_t)A.cols + 1));
-        for (int b = 0; b < 2; ++b) L.buf[b] = c.take(sizeof(ExRec) * (size_t)K.count);
-    }
-    L.total = c.off + 256;
-    return L;
-}
-
 // what both entry points ask of A and the selections
 spg_status_t ex_check(const spg_csr_t* A, const spg_sel_t* rows, const spg_sel_t* cols, ExSel& R, ExSel& K) {
     spg_status_t st = check_csr(A);
-    if (st) return st;
-    if ((st = ex_sel(rows, A->rows, R)) || (st = ex_sel(cols, A->cols, K))) return st;
-    return SPG_STATUS_SUCCESS;
+    if (!st && !(st = ex_sel(rows, A->rows, R))) st = ex_sel(cols, A->cols, K);
+    return st;
 }
 
 ExCols ex_cols(const ExSel& K, const ExLayout& L, char* ws) {
-    ExCols c;
-    c.mode = L.kmode;
-    c.start = K.start;
-    c.step = K.step;
-    c.count = K.count;
-    c.colptr = L.kmode == EX_LIST ? (const int32_t*)(ws + L.colptr) : nullptr;
-    c.colpos = L.kmode == EX_LIST ? (const ExRec*)(ws + L.buf[L.passes & 1]) : nullptr;
-    return c;
+    const bool list = L.kmode == EX_LIST;   // colptr and the sorted records exist
+    return ExCols{L.kmode, K.start, K.step, K.count, list ? (const int32_t*)(ws + L.colptr) : nullptr,
+                  list ? (const ExRec*)(ws + L.buf[sorted_buf(L.passes)]) : nullptr};
 }
 
 // colptr and the grouped positions of a column list: spg_canonicalize's passes over the records
 // (listed column, position).
 spg_status_t ex_group(spg_handle_t h, const spg_csr_t& A, const ExSel& K, const ExLayout& L, char* ws) {
-    const int64_t k = K.count, chunks = L.kchunks;
-    int64_t* scal = (int64_t*)(ws + L.scalars);
-    unsigned long long* status = (unsigned long long*)(ws + L.status_t);
-    int32_t* table = (int32_t*)(ws + L.table);
+    const int64_t k = K.count;
+    ExRec* const buf[2] = {(ExRec*)(ws + L.buf[0]), (ExRec*)(ws + L.buf[1])};
     timed_launch(h, SPG_PHASE_LAYOUT, k_ex_pack, dim3((unsigned)grid_for(k, EX_BLOCK)), dim3(EX_BLOCK), k, K.index,
-                 (ExRec*)(ws + L.buf[0]));
+                 buf[0]);
     SPG_LAUNCHED(h);
-    const dim3 grid((unsigned)grid_for(chunks, TR_WPB)), block(TR_WPB * WAVE);
-    spg_status_t st = SPG_STATUS_SUCCESS;
-    for (int p = 0; p < L.passes; ++p) {
-        const int shift = 8 * p;
-        const ExRec* in = (const ExRec*)(ws + L.buf[p & 1]);
-        timed_launch(h, SPG_PHASE_LAYOUT, k_tr_hist<int32_t, CnKeys<int32_t, uint32_t>>, grid, block, k, chunks,
-                     CnKeys<int32_t, uint32_t>{in, 0}, shift, table);
-        SPG_LAUNCHED(h);
-        if ((st = launch_scan<int32_t, int32_t>(h, TR_RADIX * chunks, table, table, status, scal, true))) return st;
-        timed_launch(h, SPG_PHASE_LAYOUT, k_cn_scatter<int32_t, uint32_t>, grid, block, k, chunks, shift, in,
-                     (const int32_t*)table, (ExRec*)(ws + L.buf[(p + 1) & 1]));
-        SPG_LAUNCHED(h);
-    }
-    const unsigned pgrid = (unsigned)std::min<int64_t>(grid_for(A.cols + 1, 256), 1 << 20);
-    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<int32_t, int32_t, CnKeys<int32_t, uint32_t>>, dim3(pgrid), dim3(256),
-                 k, A.cols, CnKeys<int32_t, uint32_t>{(const ExRec*)(ws + L.buf[L.passes & 1]), 0},
-                 (int32_t*)(ws + L.colptr), (const int32_t*)nullptr);
+    const spg_status_t st =
+        sort_records<int32_t, uint32_t>(h, k, L.kchunks, L.passes, 0, buf, (int32_t*)(ws + L.table),
+                                        (unsigned long long*)(ws + L.status_t), (int64_t*)(ws + L.scalars));
+    if (st) return st;
+    timed_launch(h, SPG_PHASE_LAYOUT, k_tr_indptr<int32_t, int32_t, CnKeys<int32_t, uint32_t>>,
+                 dim3(strided_grid(A.cols + 1, 256)), dim3(256), k, A.cols,
+                 CnKeys<int32_t, uint32_t>{(const ExRec*)buf[sorted_buf(L.passes)], 0}, (int32_t*)(ws + L.colptr),
+                 (const int32_t*)nullptr);
     SPG_LAUNCHED(h);
     return SPG_STATUS_SUCCESS;
 }
@@ -2255,16 +2055,12 @@ spg_status_t ex_structure(spg_handle_t h, const spg_csr_t& A, const ExSel& R, co
         SPG_LAUNCHED(h);
         if ((st = launch_scan<SP, SP>(h, A.nnz, S, S, (unsigned long long*)(ws + L.status_e), scal, true))) return st;
     }
-    const unsigned cgrid = (unsigned)std::min<int64_t>(grid_for(R.count, EX_BLOCK), 1 << 20);
-    timed_launch(h, SPG_PHASE_SYMBOLIC, k_ex_count<IP, SP>, dim3(cgrid), dim3(EX_BLOCK), R.count,
-                 ExRows{R.index, R.start, R.step}, (const IP*)A.indptr, (const SP*)S, cnt);
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_ex_count<IP, SP>, dim3(strided_grid(R.count, EX_BLOCK)), dim3(EX_BLOCK),
+                 R.count, ExRows{R.index, R.start, R.step}, (const IP*)A.indptr, (const SP*)S, cnt);
     SPG_LAUNCHED(h);
     if ((st = launch_scan<CP, int64_t>(h, R.count, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
         return st;
-    int64_t sc[2] = {0, 0};
-    if ((st = read_scalars(h, scal, 2, sc))) return st;
-    *nnzC = sc[0];
-    return sc[1] ? SPG_STATUS_OVERFLOW : SPG_STATUS_SUCCESS;
+    return scan_total(h, scal, nnzC);
 }
 
 template <typename IP, typename CP, typename SP, typename V>
@@ -2291,54 +2087,6 @@ spg_status_t ex_dispatch(const spg_csr_t& A, const ExLayout& L, F&& f) {
 }
 
 }  // namespace
-
-// ---- 16-bit columns for the structure broadcast (include/spgemm.h, spg_cols16_*)
-// One wave per row.  Split: every column's low half, and where the row's columns reach each
-// interior block start c * 65536 (the first entry whose high half is >= c; the row length
-// when none is).  Each start is written by exactly one lane: the entry whose high half
-// steps over it, or the tail loop for blocks past the row's last column.
-template <typename IP>
-__global__ __launch_bounds__(256) void k_cols16_split(int64_t rows, const IP* __restrict__ Mp,
-                                                      const int32_t* __restrict__ Mj, int nb1,
-                                                      uint32_t* __restrict__ starts, uint16_t* __restrict__ lo16) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = lane_id();
-    const int64_t b = (int64_t)Mp[row];
-    const uint32_t len = (uint32_t)((int64_t)Mp[row + 1] - b);
-    uint32_t* __restrict__ st = starts + row * nb1;
-    for (uint32_t i = l; i < len; i += WAVE) {
-        const uint32_t c = (uint32_t)Mj[b + i];
-        lo16[b + i] = (uint16_t)(c & 0xffffu);
-        const int hi = min((int)(c >> 16), nb1);   // (clamped: a column past M's width writes nothing past the row's starts)
-        const int hp = i ? min((int)((uint32_t)Mj[b + i - 1] >> 16), nb1) : 0;
-        for (int q = hp + 1; q <= hi; ++q) st[q - 1] = i;
-    }
-    const int hl = len ? (int)((uint32_t)Mj[b + len - 1] >> 16) : 0;
-    for (int q = hl + 1 + l; q <= nb1; q += WAVE) st[q - 1] = len;
-}
-
-// Join: column = (block << 16) | low half, the block = the number of interior starts <= the
-// entry's offset in its row (the starts ascend; a binary search over the row's nb1 starts).
-template <typename IP>
-__global__ __launch_bounds__(256) void k_cols16_join(int64_t rows, const IP* __restrict__ Mp, int nb1,
-                                                     const uint32_t* __restrict__ starts,
-                                                     const uint16_t* __restrict__ lo16, int32_t* __restrict__ Mj) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = lane_id();
-    const int64_t b = (int64_t)Mp[row];
-    const uint32_t len = (uint32_t)((int64_t)Mp[row + 1] - b);
-    const uint32_t* __restrict__ st = starts + row * nb1;
-    for (uint32_t i = l; i < len; i += WAVE) {
-        int lo = 0, hi = nb1;   // first q with st[q] > i
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (st[mid] <= i) lo = mid + 1; else hi = mid;
-        }
-        Mj[b + i] = (int32_t)(((uint32_t)lo << 16) | (uint32_t)lo16[b + i]);
-    }
-}
 
 // =============================================================================== C ABI
 extern "C" {
@@ -2768,10 +2516,7 @@ spg_status_t spg_csr2csc(spg_handle_t h, const spg_csr_t* A, spg_csr_t* AT, size
     if (!AT->indptr || (A->nnz > 0 && (!AT->indices || !AT->values))) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    if (A->nnz == 0) {   // an all-zero row pointer
-        SPG_HIP(h, hipMemsetAsync(AT->indptr, 0, index_bytes(A->indptr_type) * (size_t)(A->cols + 1), h->stream));
-        return SPG_STATUS_SUCCESS;
-    }
+    if (A->nnz == 0) return empty_structure(h, AT->indptr, A->indptr_type, A->cols + 1, nullptr);
     return dispatch_index(A->indptr_type, [&](auto ip) {
         return tr_run<decltype(ip)>(h, *A, *AT, L, ws_base(workspace));
     });
@@ -2782,18 +2527,13 @@ spg_status_t spg_csrgeam_nnz(spg_handle_t h, const spg_csr_t* A, const spg_csr_t
     if (!h) return SPG_STATUS_NOT_INITIALIZED;
     if (!workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
     spg_status_t st = gm_check(A, B);
-    if (st) return st;
-    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    if (st || (st = check_index_type(C_indptr_type))) return st;
     const GmLayout L = gm_layout(*A, *B);
     if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
     if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    if (A->rows == 0) {   // the one entry of an empty row pointer
-        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type), h->stream));
-        *nnzC = 0;
-        return SPG_STATUS_SUCCESS;
-    }
+    if (A->rows == 0) return empty_structure(h, C_indptr, C_indptr_type, 1, nnzC);   // an empty row pointer's one entry
     return dispatch_index(A->indptr_type, C_indptr_type, [&](auto ip, auto cp) {
         using CP = decltype(cp);
         return gm_structure<decltype(ip), CP>(h, *A, *B, L, ws_base(workspace), (CP*)C_indptr, nnzC);
@@ -2806,12 +2546,8 @@ spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, 
     if (!alpha || !beta || !C || !workspace) return SPG_STATUS_INVALID_VALUE;
     spg_status_t st = gm_check(A, B);
     if (st) return st;
-    if (C->rows != A->rows || C->cols != A->cols || C->value_type != A->value_type || C->nnz < 0)
-        return SPG_STATUS_INVALID_VALUE;
-    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     const GmLayout L = gm_layout(*A, *B);
-    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
-    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if ((st = check_result(C, A->rows, A->cols, A->value_type, workspace_bytes, L.total))) return st;
     if (A->rows == 0 || C->nnz == 0 || A->nnz + B->nnz == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
@@ -2833,18 +2569,14 @@ spg_status_t spg_csr_extract_nnz(spg_handle_t h, const spg_csr_t* A, const spg_s
     if (!A || !workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
     ExSel R, K;
     spg_status_t st = ex_check(A, rows, cols, R, K);
-    if (st) return st;
-    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    if (st || (st = check_index_type(C_indptr_type))) return st;
     const ExLayout L = ex_layout(*A, R, K);
     if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
     if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    if (R.count == 0 || K.count == 0 || A->nnz == 0) {   // an all-zero row pointer (nr == 0: its one entry)
-        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type) * (size_t)(R.count + 1), h->stream));
-        *nnzC = 0;
-        return SPG_STATUS_SUCCESS;
-    }
+    if (R.count == 0 || K.count == 0 || A->nnz == 0)   // an all-zero row pointer (nr == 0: its one entry)
+        return empty_structure(h, C_indptr, C_indptr_type, R.count + 1, nnzC);
     return ex_dispatch(*A, L, [&](auto ip, auto sp) {
         return dispatch_index(C_indptr_type, [&](auto cp) {
             using CP = decltype(cp);
@@ -2861,26 +2593,17 @@ spg_status_t spg_csr_extract(spg_handle_t h, const spg_csr_t* A, const spg_sel_t
     ExSel R, K;
     spg_status_t st = ex_check(A, rows, cols, R, K);
     if (st) return st;
-    if (C->rows != R.count || C->cols != K.count || C->value_type != A->value_type || C->nnz < 0)
-        return SPG_STATUS_INVALID_VALUE;
-    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     const ExLayout L = ex_layout(*A, R, K);
-    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
-    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if ((st = check_result(C, R.count, K.count, A->value_type, workspace_bytes, L.total))) return st;
     if (R.count == 0 || K.count == 0 || C->nnz == 0 || A->nnz == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
     return ex_dispatch(*A, L, [&](auto ip, auto sp) {
         return dispatch_index(C->indptr_type, [&](auto cp) {
-            auto run = [&](auto vtag) {
+            return dispatch_bits(A->value_type, [&](auto vtag) {   // values move as raw bits of their width
                 return ex_values<decltype(ip), decltype(cp), decltype(sp), decltype(vtag)>(h, *A, R, K, *C, L,
                                                                                            ws_base(workspace));
-            };
-            switch (vbytes(A->value_type)) {   // values move as raw bits of their width
-                case 4: return run(TrBits<4>::type{});
-                case 8: return run(TrBits<8>::type{});
-                default: return run(TrBits<16>::type{});
-            }
+            });
         });
     });
 }
@@ -2905,18 +2628,14 @@ spg_status_t spg_dense2csr_nnz(spg_handle_t h, const spg_dense_t* D, void* C_ind
     if (!h) return SPG_STATUS_NOT_INITIALIZED;
     if (!D || !workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
     spg_status_t st = dn_check(D);
-    if (st) return st;
-    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    if (st || (st = check_index_type(C_indptr_type))) return st;
     const DnLayout L = dn_layout(*D);
     if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
     if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    if (D->rows == 0 || D->cols == 0) {   // an all-zero row pointer
-        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type) * (size_t)(D->rows + 1), h->stream));
-        *nnzC = 0;
-        return SPG_STATUS_SUCCESS;
-    }
+    if (D->rows == 0 || D->cols == 0)   // an all-zero row pointer
+        return empty_structure(h, C_indptr, C_indptr_type, D->rows + 1, nnzC);
     return dispatch_value(D->value_type, [&](auto tag) {
         return dispatch_index(C_indptr_type, [&](auto cp) {
             using CP = decltype(cp);
@@ -2931,12 +2650,8 @@ spg_status_t spg_dense2csr(spg_handle_t h, const spg_dense_t* D, spg_csr_t* C, s
     if (!D || !C || !workspace) return SPG_STATUS_INVALID_VALUE;
     spg_status_t st = dn_check(D);
     if (st) return st;
-    if (C->rows != D->rows || C->cols != D->cols || C->value_type != D->value_type || C->nnz < 0)
-        return SPG_STATUS_INVALID_VALUE;
-    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     const DnLayout L = dn_layout(*D);
-    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
-    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if ((st = check_result(C, D->rows, D->cols, D->value_type, workspace_bytes, L.total))) return st;
     if (D->rows == 0 || D->cols == 0 || C->nnz == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
@@ -2953,18 +2668,14 @@ spg_status_t spg_canonicalize_nnz(spg_handle_t h, const spg_csr_t* A, const int3
     if (!h) return SPG_STATUS_NOT_INITIALIZED;
     if (!workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
     spg_status_t st = cn_check(A, coo_rows, ops);
-    if (st) return st;
-    if (C_indptr_type != SPG_INDEX_32I && C_indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
+    if (st || (st = check_index_type(C_indptr_type))) return st;
     const CnLayout L = cn_layout(*A, coo_rows != nullptr, ops);
     if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
     if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
     DeviceGuard dg_(h->device);
     SPG_HIP(h, dg_.err);
-    if (A->rows == 0 || A->nnz == 0) {   // an all-zero row pointer
-        SPG_HIP(h, hipMemsetAsync(C_indptr, 0, index_bytes(C_indptr_type) * (size_t)(A->rows + 1), h->stream));
-        *nnzC = 0;
-        return SPG_STATUS_SUCCESS;
-    }
+    if (A->rows == 0 || A->nnz == 0)   // an all-zero row pointer
+        return empty_structure(h, C_indptr, C_indptr_type, A->rows + 1, nnzC);
     return cn_dispatch(*A, L, [&](auto ip, auto key) {
         return dispatch_index(C_indptr_type, [&](auto cp) {
             using CP = decltype(cp);
@@ -2980,13 +2691,9 @@ spg_status_t spg_canonicalize(spg_handle_t h, const spg_csr_t* A, const int32_t*
     if (!C || !workspace) return SPG_STATUS_INVALID_VALUE;
     spg_status_t st = cn_check(A, coo_rows, ops);
     if (st) return st;
-    if (C->rows != A->rows || C->cols != A->cols || C->value_type != A->value_type || C->nnz < 0 ||
-        C->nnz > A->nnz)
-        return SPG_STATUS_INVALID_VALUE;
-    if (C->indptr_type != SPG_INDEX_32I && C->indptr_type != SPG_INDEX_64I) return SPG_STATUS_INVALID_VALUE;
     const CnLayout L = cn_layout(*A, coo_rows != nullptr, ops);
-    if (workspace_bytes < L.total) return SPG_STATUS_INVALID_VALUE;
-    if (!C->indptr || (C->nnz > 0 && (!C->indices || !C->values))) return SPG_STATUS_INVALID_VALUE;
+    if ((st = check_result(C, A->rows, A->cols, A->value_type, workspace_bytes, L.total))) return st;
+    if (C->nnz > A->nnz) return SPG_STATUS_INVALID_VALUE;   // nothing is ever added
     if (!L.marks && C->nnz != A->nnz) return SPG_STATUS_INVALID_VALUE;   // nothing is dropped: nnzC == nnz
     if (C->nnz == 0) return SPG_STATUS_SUCCESS;
     DeviceGuard dg_(h->device);
@@ -2999,11 +2706,9 @@ spg_status_t spg_canonicalize(spg_handle_t h, const spg_csr_t* A, const int32_t*
             return dispatch_value(A->value_type, [&](auto tag) {
                 return cn_values<IP, K, decltype(tag), true>(h, *A, *C, L, ws);
             });
-        switch (vbytes(A->value_type)) {   // values are moved as raw bits of their width
-            case 4: return cn_values<IP, K, TrBits<4>::type, false>(h, *A, *C, L, ws);
-            case 8: return cn_values<IP, K, TrBits<8>::type, false>(h, *A, *C, L, ws);
-            default: return cn_values<IP, K, TrBits<16>::type, false>(h, *A, *C, L, ws);
-        }
+        return dispatch_bits(A->value_type, [&](auto vtag) {   // values are moved as raw bits of their width
+            return cn_values<IP, K, decltype(vtag), false>(h, *A, *C, L, ws);
+        });
     });
 }
 

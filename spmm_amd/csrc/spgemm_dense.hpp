@@ -45,7 +45,8 @@
 #pragma once
 
 #include "spg_device.hpp"
-#include "spgemm_transpose.hpp"   // TrBits16
+#include "spg_format_layouts.hpp"   // DV_S, DV_T
+#include "spgemm_transpose.hpp"     // TrBits16
 
 namespace spg {
 
@@ -54,8 +55,7 @@ constexpr int DV_W = 512;       // csr2dense: columns of the LDS window
 constexpr int DV_R = 8;         // csr2dense: rows of the band
 constexpr int DV_PAD = 8;       // csr2dense: pad elements of an LDS row
 constexpr int DV_WBITS = 9;     // bits of a column inside the window
-constexpr int DV_S = 1024;      // dense2csr: columns per segment
-constexpr int DV_T = 64;        // dense2csr, column-major: tile edge
+// (DV_S, dense2csr's columns per segment, and DV_T, its column-major tile edge: spg_format_layouts.hpp)
 constexpr int DV_RPW = DV_T / DV_WPB;   // dense2csr, column-major: rows per wave (16)
 static_assert((1 << DV_WBITS) == DV_W, "window bits");
 static_assert(DV_S % (WAVE * 4) == 0, "a segment starts on a 16-byte chunk for every value type");

@@ -42,6 +42,7 @@
 #pragma once
 
 #include "spg_device.hpp"
+#include "spg_format_layouts.hpp" // EX_ALL / EX_RANGE / EX_LIST, EX_REC_BYTES
 #include "spgemm_canon.hpp"       // CnRec, CnKeys, the sort passes
 #include "spgemm_transpose.hpp"   // tr_row_of
 
@@ -51,9 +52,10 @@ constexpr int EX_WPB = 4;        // waves per workgroup
 constexpr int EX_CHUNK = 1024;   // output entries per wave chunk (16 steps of 64)
 constexpr int EX_BLOCK = 256;
 
-constexpr int EX_ALL = 0, EX_RANGE = 1, EX_LIST = 2;
+// (EX_ALL / EX_RANGE / EX_LIST, the column selection's mode: spg_format_layouts.hpp)
 
 using ExRec = CnRec<int32_t, uint32_t>;   // (listed column, position in the list)
+static_assert(sizeof(ExRec) == EX_REC_BYTES, "ex_layout's record size");
 
 // The row selection: sel_r(i).
 struct ExRows {

@@ -35,12 +35,12 @@
 #pragma once
 
 #include "spg_device.hpp"
-#include "spgemm_transpose.hpp"   // tr_row_of
+#include "spg_format_layouts.hpp"   // GM_CHUNK (entries per wave chunk)
+#include "spgemm_transpose.hpp"     // tr_row_of
 
 namespace spg {
 
 constexpr int GM_WPB = 4;                            // waves per workgroup
-constexpr int GM_CHUNK = 1024;                       // entries per wave chunk (16 steps of 64)
 
 // The first position in [lo, hi) of Xj whose column is >= col (hi when there is none).
 __device__ __forceinline__ int64_t gm_lower_bound(const int32_t* __restrict__ Xj, int64_t lo, int64_t hi,

@@ -4,11 +4,11 @@
 #pragma once
 
 #include "spg_device.hpp"
+#include "spg_format_layouts.hpp"   // WPB, BLOCK, SCAN_ITEMS, SCAN_TILE
 
 namespace spg {
 
-constexpr int WPB = 4;              // waves per block
-constexpr int BLOCK = WPB * WAVE;   // 256 threads
+static_assert(BLOCK == WPB * WAVE, "a block is WPB waves");
 
 // ---------------------------------------------------------------------------------------
 // P_i = number of products of output row i (workEstimation).  One wave per row.
@@ -740,9 +740,8 @@ __global__ __launch_bounds__(G::WPB * WAVE, sizeof(T) <= 8 ? 5 : 2) void k_short
 // Status word: bits 63..62 = 0 not ready / 1 tile aggregate / 2 inclusive prefix,
 // bits 61..0 = value.  Tiles take tickets in order, so every tile a block waits on has
 // started; the status word is its own payload (8-byte agent-scope atomics on both sides,
-// MI355X_MICROARCH.md, "Valid forms").
-constexpr int SCAN_ITEMS = 8;
-constexpr int SCAN_TILE = BLOCK * SCAN_ITEMS;   // 2048
+// MI355X_MICROARCH.md, "Valid forms").  A tile is SCAN_TILE = BLOCK * SCAN_ITEMS elements
+// (spg_format_layouts.hpp: the carves size the status words by it).
 // word of the host-pinned buffer that carries the generation of the last mirrored scan (past
 // every word read_scalars fills)
 constexpr int MIRROR_GEN_WORD = 16 + 1024;

@@ -35,13 +35,12 @@
 #pragma once
 
 #include "spg_device.hpp"
+#include "spg_format_layouts.hpp"   // TR_CHUNK (entries per wave chunk), TR_RADIX (8-bit digits)
 
 namespace spg {
 
 constexpr int TR_WPB = 4;                          // waves per workgroup
-constexpr int TR_CHUNK = 2048;                     // entries per wave chunk
 constexpr int TR_BLOCK_ENTRIES = TR_WPB * TR_CHUNK;   // entries per workgroup (8192)
-constexpr int TR_RADIX = 256;                      // 8-bit digits
 
 // Raw bits of a value: 4, 8 or 16 bytes.  (8-byte alignment: a complex128 array is only promised
 // its component's alignment; gfx950 takes the 16 bytes as one access all the same.)

@@ -551,35 +551,50 @@ def first_bit_difference(got, want):
 # ---- device bytes per test at a geometry: the arrays the test allocates (the library's own answer
 # ---- to the size query is added by the test, and estimated here for the cap)
 
+def workspace_share(g):
+    """{test: the bytes of planned_bytes' figure that stand for the library's workspaces}.  They
+    restate the carves of spmm_amd/csrc/spg_format_layouts.hpp for int64 positions, per entry: a
+    digit table of 1 byte (256 counters of 8 bytes per 2048 entries), the transpose's sorted
+    columns 4, a sort's two record buffers 16 each, the kept marks 8, the addition's marks 8 per
+    entry of its second operand and 8 per row, the dense table 8 per row; the look-back words,
+    scalars and alignment are covered by 1 % on top.  tests/test_format_layouts_cpu.py holds the
+    carves themselves under these figures."""
+    def ws(per_entry, per_row=0):
+        return int(1.01 * (per_entry * g.nnz + per_row * g.rows))
+    return {
+        "csr2csc": ws(1 + 4),
+        "csrgeam": ws(8, 48),                    # the swapped roles mark all of A
+        "canonicalize_sum": ws(1 + 8 + 32),      # table + marks + records
+        "canonicalize_drop": ws(8),
+        "canonicalize_coo": ws(1 + 32),
+        "dense": ws(0, 8),                       # the table
+        "shim": ws(0, 24),
+    }
+
+
 def planned_bytes(g):
     """{test: device bytes it needs beyond the shared forward operand}, plus "operand" itself: the
     arrays the test allocates, the temporaries of one slice ("validate" is those alone) and the
-    workspace.  The workspaces restate the carves of spgemm.hip for int64 positions, per entry:
-    a digit table of 1 byte (256 counters of 8 bytes per 2048 entries), the transpose's sorted
-    columns 4, a sort's two record buffers 16 each, the kept marks 8, the addition's marks 8 per
-    entry of its second operand and 8 per row, the dense table 8 per row; the look-back words,
-    scalars and alignment are covered by 1 % on top, everything small by 256 MiB.  The GPU tests print what the size queries
-    answer and add that instead."""
+    workspace (workspace_share); everything small is covered by 256 MiB.  The GPU tests print what
+    the size queries answer and add that instead."""
     A = g.csr_bytes()
     n = g.nnz
     slice_tmp = 16 * 8 * g.slice_entries
     dense = g.rows * g.W * 4
-
-    def ws(per_entry, per_row=0):
-        return int(1.01 * (per_entry * n + per_row * g.rows))
+    ws = workspace_share(g)
     slack = 1 << 28          # guard bands, small operands, the dense operands of the products
     plan = {
         "operand": A,
         "validate": slice_tmp,
         "spmv": 2 * g.rows * 4 + slice_tmp,
         "spmm": 2 * g.rows * 33 * 4 + slice_tmp,
-        "csr2csc": A + ws(1 + 4) + slice_tmp,
-        "csrgeam": 2 * A + ws(8, 48) + slice_tmp,                   # two results; the swapped roles mark all of A
-        "canonicalize_sum": 2 * A + ws(1 + 8 + 32) + slice_tmp,     # the input, C, table + marks + records
-        "canonicalize_drop": 2 * A + ws(8) + slice_tmp,
-        "canonicalize_coo": A + 12 * n + ws(1 + 32) + slice_tmp,
-        "dense": 2 * dense + A + ws(0, 8) + slice_tmp,              # D in both orders, C, the table
-        "cols16": (4 + 2 + 4) * n + 16 * g.rows + slice_tmp,        # wide indices, lo16, joined indices, starts
-        "shim": dense + A + ws(0, 24) + slice_tmp,
+        "csr2csc": A + ws["csr2csc"] + slice_tmp,
+        "csrgeam": 2 * A + ws["csrgeam"] + slice_tmp,                     # two results
+        "canonicalize_sum": 2 * A + ws["canonicalize_sum"] + slice_tmp,   # the input, C
+        "canonicalize_drop": 2 * A + ws["canonicalize_drop"] + slice_tmp,
+        "canonicalize_coo": A + 12 * n + ws["canonicalize_coo"] + slice_tmp,
+        "dense": 2 * dense + A + ws["dense"] + slice_tmp,                 # D in both orders, C
+        "cols16": (4 + 2 + 4) * n + 16 * g.rows + slice_tmp,              # wide indices, lo16, joined indices, starts
+        "shim": dense + A + ws["shim"] + slice_tmp,
     }
     return {k: v + (slack if k not in ("operand", "validate") else 0) for k, v in plan.items()}

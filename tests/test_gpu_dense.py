@@ -41,9 +41,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_constants_mirror_the_kernels():
-    text = open(os.path.join(ROOT, "spmm_amd", "csrc", "spgemm_dense.hpp")).read()
-    for name, v in (("DV_W", W), ("DV_R", R), ("DV_S", S), ("DV_T", T)):
-        assert f"constexpr int {name} = {v};" in text, name
+    # (DV_S and DV_T size dn_layout's table too: the kernels take them from the carves' header)
+    for header, names in (("spgemm_dense.hpp", (("DV_W", W), ("DV_R", R))),
+                          ("spg_format_layouts.hpp", (("DV_S", S), ("DV_T", T)))):
+        text = open(os.path.join(ROOT, "spmm_amd", "csrc", header)).read()
+        for name, v in names:
+            assert f"constexpr int {name} = {v};" in text, name
+    assert '#include "spg_format_layouts.hpp"' in open(os.path.join(ROOT, "spmm_amd", "csrc", "spgemm_dense.hpp")).read()
 
 
 def _handle():

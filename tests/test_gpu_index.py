@@ -197,6 +197,33 @@ def test_column_list_sort_seams(k):
     ic.same_arrays(ic.expected(S, rows, cols), _run(A, rows, cols))
 
 
+@functools.lru_cache(maxsize=None)
+def _pass_count_case(width):
+    """A of 40 rows and about 600 entries over `width` columns, a list of 300 positions with
+    repeats (four in five of them columns A holds), and index_cases.expected of A[:, list]."""
+    rng = np.random.default_rng(width)
+    rows = [np.sort(rng.choice(width, int(n), replace=False)) for n in rng.integers(0, 31, 40)]
+    indptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    indices = np.concatenate(rows).astype(np.int32)
+    S = sp.csr_matrix((rng.standard_normal(indices.size), indices, indptr), shape=(40, width))
+    held = rng.choice(indices, 60)
+    picks = np.where(rng.random(300) < 0.8, rng.choice(held, 300), rng.integers(0, width, 300))
+    cols = ("list", [int(v) for v in picks])
+    assert len(set(cols[1])) < 300 and max(cols[1]) >= (width - 1) // 2
+    return S, cols, ic.expected(S, None, cols)
+
+
+@pytest.mark.parametrize("ipcp", [IPCP[0], IPCP[3]], ids=_ipcp_id)
+@pytest.mark.parametrize("width,passes", [(200, 1), (70000, 3), ((1 << 24) + 3, 4)])
+def test_column_list_sort_pass_counts(width, passes, ipcp):
+    """The list's sort over one, three and four digit passes (the bytes of width - 1): the sorted
+    records end in one ping-pong buffer or the other by the parity of the pass count."""
+    assert (max(width - 1, 1).bit_length() + 7) // 8 == passes
+    S, cols, want = _pass_count_case(width)
+    assert want[1].size >= 200
+    ic.same_arrays(want, _run(_Operand(S, ipcp[0]), None, cols, ipcp[1]), f"{passes} passes")
+
+
 @pytest.mark.parametrize("nr", [2047, 2048, 2049])
 def test_row_scan_seams(nr):
     """The scan over the output rows at one tile and one row past it."""
