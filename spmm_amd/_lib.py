@@ -52,6 +52,14 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_csrgeam_nnz", "spg_csrgeam", "spg_canonicalize_nnz", "spg_canonicalize",
            "spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr", "spg_csr_extract_nnz", "spg_csr_extract")
 
+# the entry points of the format operations, added within 0.2.0: an older development build
+# (SPG_LIB) may lack them, and the containers then keep their torch form (exports)
+CSR2CSC = ("spg_csr2csc",)
+CSRGEAM = ("spg_csrgeam_nnz", "spg_csrgeam")
+CANONICALIZE = ("spg_canonicalize_nnz", "spg_canonicalize")
+EXTRACT = ("spg_csr_extract_nnz", "spg_csr_extract")
+DENSE_CONVERT = ("spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr")
+
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
 
@@ -173,6 +181,12 @@ def load():
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+def exports(*symbols: str) -> bool:
+    """True when the loaded library exports every one of these symbols."""
+    lib = load()
+    return all(hasattr(lib, s) for s in symbols)
 
 
 _build_id = None

@@ -19,7 +19,9 @@ current torch stream.  The result's ``indptr`` is int32 when nnz(C) < 2**31, int
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -27,7 +29,7 @@ import torch
 
 from . import _fastpath, _lib
 from ._lib import SpgCsr, SpgError, check
-from .sparse import csr_matrix
+from .sparse import _axis_selector, _indptr_dtype, coo_matrix, csc_matrix, csr_matrix
 
 _VT = {torch.float32: _lib.SPG_R_32F, torch.float64: _lib.SPG_R_64F,
        torch.complex64: _lib.SPG_C_32F, torch.complex128: _lib.SPG_C_64F}
@@ -72,10 +74,36 @@ def check_availability(name: str) -> bool:
     return _available
 
 
+def _check_type(x, kinds) -> None:
+    if not isinstance(x, kinds):
+        raise TypeError("unsupported type (actual: {})".format(type(x)))
+
+
+def _check_device(x, name: str) -> None:
+    if x.device.type != "cuda":
+        raise RuntimeError(f"{name} needs device-resident operands")
+
+
+def _guard(name: str, x=None, kinds=None) -> None:
+    """What a public function opens with, in this order: the routine can run here, and (with
+    `kinds`) its operand has one of these types and sits on a GPU."""
+    if not check_availability(name):
+        raise RuntimeError(f"{name} is not available.")
+    if kinds is not None:
+        _check_type(x, kinds)
+        _check_device(x, name)
+
+
+def _view(rows, cols, nnz, indptr, indices, data, dtype, index_dtype=None) -> SpgCsr:
+    """The spg_csr_t of CSR arrays; an empty matrix has null indices and values.  ``data`` None:
+    the structure alone.  ``indptr`` None (COO input): no row pointer, of type `index_dtype`."""
+    return SpgCsr(rows, cols, nnz, indptr.data_ptr() if indptr is not None else 0,
+                  indices.data_ptr() if nnz else 0, data.data_ptr() if nnz and data is not None else 0,
+                  _IT[index_dtype or indptr.dtype], _VT[dtype])
+
+
 def _csr_view(m: csr_matrix) -> SpgCsr:
-    return SpgCsr(m.shape[0], m.shape[1], m.nnz, m.indptr.data_ptr(),
-                  m.indices.data_ptr() if m.nnz else 0, m.data.data_ptr() if m.nnz else 0,
-                  _IT[m.indptr.dtype], _VT[m.data.dtype])
+    return _view(m.shape[0], m.shape[1], m.nnz, m.indptr, m.indices, m.data, m.data.dtype)
 
 
 def _current_stream_ptr(dev: int) -> int:
@@ -83,18 +111,100 @@ def _current_stream_ptr(dev: int) -> int:
     return raw(dev) if raw is not None else torch.cuda.current_stream(dev).cuda_stream
 
 
-def _handle_for(m: csr_matrix) -> _lib.Handle:
-    d = m.device
-    dev = d.index if d.index is not None else torch.cuda.current_device()
-    h = _lib.get_handle(dev)
-    h.set_stream(_current_stream_ptr(dev))
+def _handle_on(dev) -> _lib.Handle:
+    """This thread's handle for the device of `dev`, set to the current torch stream."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    h = _lib.get_handle(idx)
+    h.set_stream(_current_stream_ptr(idx))
     return h
+
+
+def _handle_for(m: csr_matrix) -> _lib.Handle:
+    return _handle_on(m.device)
+
+
+def _alpha_of(dtype, alpha):
+    """A host scalar of the value type: one number, or a (real, imag) pair for complex."""
+    ct, nparts = _ALPHA_CT[dtype]
+    return (ct * 2)(complex(alpha).real, complex(alpha).imag) if nparts == 2 else ct(float(alpha))
+
+
+def _sized_workspace(call, where: str, dev, verbose_alg=None):
+    """The size query ``call(byref(ws_bytes), None)`` and a workspace of that size:
+    (ws, ws_bytes, its pointer).  The caller keeps `ws` until its last call with it is queued."""
+    ws_bytes = ctypes.c_size_t(0)
+    check(call(ctypes.byref(ws_bytes), None), where)
+    if verbose_alg is not None:
+        print("USING ALG", verbose_alg, "workspace GB =", ws_bytes.value / (1024 ** 3))
+    # from torch's caching allocator on the current stream (the library works on that stream,
+    # so a later reuse of the block is ordered after this operation)
+    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
+    return ws, ws_bytes, ctypes.c_void_p(ws.data_ptr())
+
+
+def _structure(call, rows: int, indptr_dtypes, dev):
+    """``call(row pointer, its index type)`` into a fresh row pointer of each dtype in turn
+    while the answer is OVERFLOW (nnz(C) past int32): (the last status, the row pointer)."""
+    for it in indptr_dtypes:
+        indptr = torch.empty(rows + 1, dtype=it, device=dev)
+        st = call(ctypes.c_void_p(indptr.data_ptr()), _IT[it])
+        if st != _lib.STATUS_OVERFLOW:
+            break
+    return st, indptr
+
+
+def _empty_c(rows, cols, nnz, indptr, dtype, dev):
+    """(data, indices, view) of a result whose row pointer is filled: its arrays, to be written."""
+    indices = torch.empty(nnz, dtype=torch.int32, device=dev)
+    data = torch.empty(nnz, dtype=dtype, device=dev)
+    return data, indices, _view(rows, cols, nnz, indptr, indices, data, dtype)
+
+
+def _two_phase(h, names, sargs, vargs, rows, cols, dtype, indptr_dtypes, dev):
+    """The frame of a format operation with a structure call and a value call (include/spgemm.h):
+
+        names[0](h, *sargs, C's row pointer, its index type, &nnz, &ws_bytes, ws)
+        names[1](h, *vargs, C, ws_bytes, ws)
+
+    The size query (null pointers, the first of `indptr_dtypes`), the workspace, the structure
+    call -- once more per further dtype while it answers OVERFLOW; one dtype: OVERFLOW raises --
+    then C's arrays, rows x cols of `dtype`, and the value call.  `vargs` may be a callable that
+    gives them: it runs after the structure call (csrgeam2 converts its scalars there).
+    (data, indices, indptr) of C."""
+    structure = functools.partial(getattr(h.lib, names[0]), h.ptr, *sargs)
+    nnz = ctypes.c_int64(0)
+    nnz_p, it0 = ctypes.byref(nnz), _IT[indptr_dtypes[0]]
+    ws, ws_bytes, wp = _sized_workspace(lambda wb, p: structure(None, it0, nnz_p, wb, p), names[0], dev)
+    wb = ctypes.byref(ws_bytes)
+    st, indptr = _structure(lambda ip, it: structure(ip, it, nnz_p, wb, wp), rows, indptr_dtypes, dev)
+    check(st, names[0])
+    data, indices, vc = _empty_c(rows, cols, int(nnz.value), indptr, dtype, dev)
+    vargs = vargs() if callable(vargs) else vargs
+    check(getattr(h.lib, names[1])(h.ptr, *vargs, ctypes.byref(vc), ws_bytes, wp), names[1])
+    return data, indices, indptr
+
+
+@contextlib.contextmanager
+def _planned(h, a, b, algo, cf, verbose_alg=None):
+    """spg_plan (size query) -> workspace -> spg_plan (build): (plan, workspace bytes) for the
+    block, with the workspace and the operand views kept; spg_plan_destroy on the way out."""
+    va, vb = _csr_view(a), _csr_view(b)
+    plan = ctypes.c_void_p()
+
+    def call(ws_bytes, ws):
+        return h.lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ws_bytes, ws,
+                              None if ws is None else ctypes.byref(plan))
+    ws, ws_bytes, wp = _sized_workspace(call, "spg_plan", a.device, verbose_alg)
+    check(call(ctypes.byref(ws_bytes), wp), "spg_plan")
+    try:
+        yield plan, ws_bytes.value
+    finally:
+        h.lib.spg_plan_destroy(plan)
 
 
 def validate_csr(m: csr_matrix) -> int:
     """1 canonical, 0 unsorted/duplicates, -1 malformed (spg_validate_csr)."""
-    if m.device.type != "cuda":
-        raise RuntimeError("validate_csr needs device-resident operands")
+    _check_device(m, "validate_csr")
     h = _handle_for(m)
     v = _csr_view(m)
     res = ctypes.c_int(0)
@@ -113,8 +223,7 @@ def _cols16_split(m: csr_matrix):
     starts = torch.empty((rows, nb1), dtype=torch.int32, device=m.device)
     lo16 = torch.empty(m.nnz, dtype=torch.int16, device=m.device)
     h = _handle_for(m)
-    v = SpgCsr(rows, m.shape[1], m.nnz, m.indptr.data_ptr(), m.indices.data_ptr() if m.nnz else 0, 0,
-               _IT[m.indptr.dtype], _VT[torch.float64])
+    v = _view(rows, m.shape[1], m.nnz, m.indptr, m.indices, None, torch.float64)
     check(h.lib.spg_cols16_split(h.ptr, ctypes.byref(v), ctypes.c_void_p(starts.data_ptr() if starts.numel() else 0),
                                  ctypes.c_void_p(lo16.data_ptr() if m.nnz else 0)), "spg_cols16_split")
     return starts, lo16
@@ -125,11 +234,8 @@ def _cols16_join(indptr: torch.Tensor, starts: torch.Tensor, lo16: torch.Tensor,
     rows, cols = shape
     nnz = lo16.numel()
     out = torch.empty(nnz, dtype=torch.int32, device=indptr.device)
-    dev = indptr.device.index if indptr.device.index is not None else torch.cuda.current_device()
-    h = _lib.get_handle(dev)
-    h.set_stream(_current_stream_ptr(dev))
-    v = SpgCsr(rows, cols, nnz, indptr.data_ptr(), out.data_ptr() if nnz else 0, 0, _IT[indptr.dtype],
-               _VT[torch.float64])
+    h = _handle_on(indptr.device)
+    v = _view(rows, cols, nnz, indptr, out, None, torch.float64)
     check(h.lib.spg_cols16_join(h.ptr, ctypes.byref(v), ctypes.c_void_p(starts.data_ptr() if starts.numel() else 0),
                                 ctypes.c_void_p(lo16.data_ptr() if nnz else 0)), "spg_cols16_join")
     return out
@@ -183,13 +289,10 @@ def _spgemm(a, b, alpha=1, alg=0, chunk_fraction=0.2, verbose=False, before_nume
     values permuted tile-major by this plan, dtype: the plan's value type) and `by_tiles` returns (tm, groups): the
     tile-major values tensor and an iterable of (tile_begin, tile_end) ranges, each yielded
     once its slice of tm is ready on the current stream, together covering every tile."""
-    if not check_availability("spgemm"):
-        raise RuntimeError("spgemm is not available.")
+    _guard("spgemm")
     assert a.ndim == b.ndim == 2
-    if not isinstance(a, csr_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(a)))
-    if not isinstance(b, csr_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(b)))
+    _check_type(a, csr_matrix)
+    _check_type(b, csr_matrix)
     assert a.has_canonical_format
     assert b.has_canonical_format
     if a.shape[1] != b.shape[0]:
@@ -203,6 +306,7 @@ def _spgemm(a, b, alpha=1, alg=0, chunk_fraction=0.2, verbose=False, before_nume
     if a.indptr.dtype != b.indptr.dtype:   # the engine takes one row-pointer type for A and B
         a = csr_matrix((a.data, a.indices, a.indptr.to(torch.int64)), shape=a.shape, canonical=True)
         b = csr_matrix((b.data, b.indices, b.indptr.to(torch.int64)), shape=b.shape, canonical=True)
+        # (the constructor narrows a row pointer that fits back to int32: this is what widens them)
         a.indptr, b.indptr = a.indptr.to(torch.int64), b.indptr.to(torch.int64)
     algo = _ALG.get(alg, _lib.SPG_ALG_DEFAULT)
     if algo == _lib.SPG_ALG3 and not (0.0 < float(chunk_fraction) <= 1.0):
@@ -229,35 +333,21 @@ def _spgemm(a, b, alpha=1, alg=0, chunk_fraction=0.2, verbose=False, before_nume
         check(st, "spg_spgemm_ws")
         if verbose:
             print("USING ALG", alg, "workspace GB =", wsb / (1024 ** 3))
-        last_stats.alg, last_stats.workspace_bytes = int(algo), int(wsb)
-        last_stats.peak_bytes, last_stats.nnz = int(peak), int(indices.numel())
-        return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True)
+        return _product(data, indices, indptr, (m, n), False, algo, wsb, peak)
     lib = h.lib
     va, vb = _csr_view(a), _csr_view(b)
-    ws_bytes = ctypes.c_size_t(0)
-    check(lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf,
-                       ctypes.byref(ws_bytes), None, None), "spg_plan")
-    if verbose:
-        print("USING ALG", alg, "workspace GB =", ws_bytes.value / (1024 ** 3))
-    # workspace from torch's caching allocator on the current stream (the library works on
-    # that stream, so a later reuse of the block is ordered after this product)
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    ct, nparts = _ALPHA_CT[a.data.dtype]
-    al = (ct * 2)(complex(alpha).real, complex(alpha).imag) if nparts == 2 else ct(float(alpha))
+    ws, ws_bytes, wp = _sized_workspace(
+        lambda wb, p: lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, wb, p, None),
+        "spg_plan", dev, alg if verbose else None)
+    al = _alpha_of(a.data.dtype, alpha)
     nnz, peak = ctypes.c_int64(0), ctypes.c_size_t(0)
     pj, px, plan = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
     # plan -> symbolic (nnz(C) to the host) -> numeric in one call (spg_spgemm_ws)
-    # int64 row pointer once nnz(C) >= 2**31; int64 first when the expected product count
-    # reaches 2**31 (an overflowing int32 try would redo the plan and the symbolic pass)
-    wide = a.nnz * (b.nnz / max(b.shape[0], 1)) >= 2 ** 31
-    for it in ((torch.int64,) if wide else (torch.int32, torch.int64)):
-        indptr = torch.empty(m + 1, dtype=it, device=dev)
-        st = lib.spg_spgemm_ws(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ctypes.byref(al),
-                               ctypes.c_void_p(ws.data_ptr()), ws_bytes.value,
-                               ctypes.c_void_p(indptr.data_ptr()), _IT[it], ctypes.byref(nnz),
-                               ctypes.byref(pj), ctypes.byref(px), ctypes.byref(peak), ctypes.byref(plan))
-        if st != _lib.STATUS_OVERFLOW:
-            break
+    wide, tries = _indptr_tries(a, b)
+    st, indptr = _structure(
+        lambda ip, it: lib.spg_spgemm_ws(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ctypes.byref(al), wp,
+                                         ws_bytes.value, ip, it, ctypes.byref(nnz), ctypes.byref(pj),
+                                         ctypes.byref(px), ctypes.byref(peak), ctypes.byref(plan)), m, tries, dev)
     check(st, "spg_spgemm_ws")
     nnzc = int(nnz.value)
     if pj.value:
@@ -268,25 +358,31 @@ def _spgemm(a, b, alpha=1, alg=0, chunk_fraction=0.2, verbose=False, before_nume
         data = ws[ox:ox + a.data.element_size() * nnzc].view(a.data.dtype)
     else:
         try:
-            indices = torch.empty(nnzc, dtype=torch.int32, device=dev)
-            data = torch.empty(nnzc, dtype=a.data.dtype, device=dev)
-            vc = SpgCsr(m, n, nnzc, indptr.data_ptr(), indices.data_ptr() if nnzc else 0,
-                        data.data_ptr() if nnzc else 0, _IT[indptr.dtype], _VT[data.dtype])
+            data, indices, vc = _empty_c(m, n, nnzc, indptr, a.data.dtype, dev)
             if before_numeric is not None:
                 before_numeric()
             check(lib.spg_numeric(h.ptr, plan, ctypes.byref(al), ctypes.byref(vc)), "spg_numeric")
         finally:
             lib.spg_plan_destroy(plan)
+    return _product(data, indices, indptr, (m, n), wide, algo, ws_bytes.value, peak.value)
+
+
+def _indptr_tries(a, b):
+    """(wide, the row-pointer dtypes to try) of a product: int64 once nnz(C) >= 2**31, and int64
+    first (`wide`) when the expected product count reaches 2**31 -- an overflowing int32 try
+    would redo the plan and the symbolic pass."""
+    wide = a.nnz * (b.nnz / max(b.shape[0], 1)) >= 2 ** 31
+    return wide, ((torch.int64,) if wide else (torch.int32, torch.int64))
+
+
+def _product(data, indices, indptr, shape, wide, algo, ws_bytes, peak):
+    """The product's csr_matrix, its accounting left in last_stats."""
+    nnzc = int(indices.numel())
     if wide and nnzc < 2 ** 31:
         indptr = indptr.to(torch.int32)   # the int32 contract when the result fits
-    last_stats.alg, last_stats.workspace_bytes = int(algo), int(ws_bytes.value)
-    last_stats.peak_bytes, last_stats.nnz = int(peak.value), nnzc
-    return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True)
-
-
-def _alpha_of(dtype, alpha):
-    ct, nparts = _ALPHA_CT[dtype]
-    return (ct * 2)(complex(alpha).real, complex(alpha).imag) if nparts == 2 else ct(float(alpha))
+    last_stats.alg, last_stats.workspace_bytes = int(algo), int(ws_bytes)
+    last_stats.peak_bytes, last_stats.nnz = int(peak), nnzc
+    return csr_matrix._from_parts(data, indices, indptr, shape, canonical=True)
 
 
 def _spgemm_by_tiles(h, a, b, alpha, algo, cf, by_tiles, verbose, values_first=True):
@@ -298,52 +394,28 @@ def _spgemm_by_tiles(h, a, b, alpha, algo, cf, by_tiles, verbose, values_first=T
     lib = h.lib
     m, n = a.shape[0], b.shape[1]
     dev = a.device
-    va, vb = _csr_view(a), _csr_view(b)
-    ws_bytes = ctypes.c_size_t(0)
-    check(lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ctypes.byref(ws_bytes), None, None),
-          "spg_plan")
-    if verbose:
-        print("USING ALG", algo, "workspace GB =", ws_bytes.value / (1024 ** 3))
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    plan = ctypes.c_void_p()
-    check(lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, cf, ctypes.byref(ws_bytes),
-                       ctypes.c_void_p(ws.data_ptr()), ctypes.byref(plan)), "spg_plan")
-    al = _alpha_of(a.data.dtype, alpha)
-    try:
+    with _planned(h, a, b, algo, cf, algo if verbose else None) as (plan, ws_bytes):
+        al = _alpha_of(a.data.dtype, alpha)
         if values_first:
             geom = _tile_geometry(h, plan, b)
             got = by_tiles(geom)
         nnz = ctypes.c_int64(0)
-        wide = a.nnz * (b.nnz / max(b.shape[0], 1)) >= 2 ** 31
-        for it in ((torch.int64,) if wide else (torch.int32, torch.int64)):
-            indptr = torch.empty(m + 1, dtype=it, device=dev)
-            st = lib.spg_symbolic(h.ptr, plan, ctypes.c_void_p(indptr.data_ptr()), _IT[it], ctypes.byref(nnz))
-            if st != _lib.STATUS_OVERFLOW:
-                break
+        wide, tries = _indptr_tries(a, b)
+        st, indptr = _structure(lambda ip, it: lib.spg_symbolic(h.ptr, plan, ip, it, ctypes.byref(nnz)), m, tries, dev)
         check(st, "spg_symbolic")
         if not values_first:
             geom = _tile_geometry(h, plan, b)
             got = by_tiles(geom)
         if got is not None and geom is None:
             raise RuntimeError("by_tiles returned tile groups for a plan that cannot run by tiles")
-        nnzc = int(nnz.value)
-        indices = torch.empty(nnzc, dtype=torch.int32, device=dev)
-        data = torch.empty(nnzc, dtype=a.data.dtype, device=dev)
-        vc = SpgCsr(m, n, nnzc, indptr.data_ptr(), indices.data_ptr() if nnzc else 0,
-                    data.data_ptr() if nnzc else 0, _IT[indptr.dtype], _VT[data.dtype])
+        data, indices, vc = _empty_c(m, n, int(nnz.value), indptr, a.data.dtype, dev)
         if got is None:
             check(lib.spg_numeric(h.ptr, plan, ctypes.byref(al), ctypes.byref(vc)), "spg_numeric")
         else:
             _numeric_groups(h, plan, al, vc, got, geom)
         peak = ctypes.c_size_t(0)
         check(lib.spg_peak_bytes(plan, ctypes.byref(peak)), "spg_peak_bytes")
-    finally:
-        lib.spg_plan_destroy(plan)
-    if wide and nnzc < 2 ** 31:
-        indptr = indptr.to(torch.int32)   # the int32 contract when the result fits
-    last_stats.alg, last_stats.workspace_bytes = int(algo), int(ws_bytes.value)
-    last_stats.peak_bytes, last_stats.nnz = int(peak.value), nnzc
-    return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True)
+    return _product(data, indices, indptr, (m, n), wide, algo, ws_bytes, peak.value)
 
 
 def _tile_geometry(h, plan, b):
@@ -388,6 +460,27 @@ def _numeric_groups(h, plan, al, vc, got, geom):
         raise RuntimeError(f"tile groups covered {covered} of {geom['tiles']} tiles")
 
 
+def _sparse_operand(name: str, a, transa: bool):
+    """(A as a csr_matrix, transa) of spmv's / spmm's sparse operand: a CSC matrix goes through
+    its free transpose with ``transa`` flipped (as the reference does), a COO matrix through CSR."""
+    _guard(name)
+    if isinstance(a, csc_matrix):
+        a = a.T
+        transa = not transa
+    _check_type(a, (csr_matrix, coo_matrix))
+    if isinstance(a, coo_matrix):
+        a = a.tocsr()
+    return a, transa
+
+
+def _promoted(name: str, a, dense_dtype):
+    """A in the common value type of A and the dense operand."""
+    dt = np.promote_types(a.dtype, np.dtype(str(dense_dtype).replace("torch.", "")))
+    if dt not in (np.float32, np.float64, np.complex64, np.complex128):
+        raise TypeError(f"{name} supports float32/float64/complex64/complex128, got {dt}")
+    return a.astype(dt)
+
+
 def spmv(a, x, y=None, alpha=1, beta=0, transa=False):
     """y = alpha * op(A) x + beta * y -- the drop-in for ``cupyx.cusparse.spmv``
     (modify_src/cupy-src/cupyx/cusparse.py:1373-1432), on ``spg_spmv``.
@@ -398,16 +491,7 @@ def spmv(a, x, y=None, alpha=1, beta=0, transa=False):
     ``transa=True`` and a CSC operand against scipy's ``A.T @ x`` / ``A @ x``: the transpose is
     spg_csr2csc's stable counting sort, scipy's own (csr_tocsc), so the sums keep scipy's order.
     """
-    from .sparse import coo_matrix, csc_matrix
-    if not check_availability("spmv"):
-        raise RuntimeError("spmv is not available.")
-    if isinstance(a, csc_matrix):
-        a = a.T
-        transa = not transa
-    if not isinstance(a, (csr_matrix, coo_matrix)):
-        raise TypeError("unsupported type (actual: {})".format(type(a)))
-    if isinstance(a, coo_matrix):
-        a = a.tocsr()
+    a, transa = _sparse_operand("spmv", a, transa)
     if transa:
         a = a.transpose_csr()
     dev = a.device
@@ -418,10 +502,7 @@ def spmv(a, x, y=None, alpha=1, beta=0, transa=False):
         raise ValueError("dimension mismatch")
     assert a.has_canonical_format
     m = a.shape[0]
-    dt = np.promote_types(a.dtype, np.dtype(str(x.dtype).replace("torch.", "")))
-    if dt not in (np.float32, np.float64, np.complex64, np.complex128):
-        raise TypeError(f"spmv supports float32/float64/complex64/complex128, got {dt}")
-    a = a.astype(dt)
+    a = _promoted("spmv", a, x.dtype)
     tdt = a.data.dtype
     x = x.to(tdt).contiguous()
     if y is None:
@@ -436,10 +517,7 @@ def spmv(a, x, y=None, alpha=1, beta=0, transa=False):
         return y
     h = _handle_for(a)
     va = _csr_view(a)
-    ct, nparts = _ALPHA_CT[tdt]
-    def host(v):
-        return (ct * 2)(complex(v).real, complex(v).imag) if nparts == 2 else ct(float(v))
-    al, be = host(alpha), host(beta)
+    al, be = _alpha_of(tdt, alpha), _alpha_of(tdt, beta)
     check(h.lib.spg_spmv(h.ptr, ctypes.byref(va), ctypes.c_void_p(x.data_ptr()), ctypes.byref(al),
                          ctypes.byref(be), ctypes.c_void_p(y.data_ptr())), "spg_spmv")
     return y
@@ -483,16 +561,7 @@ def spmm(a, b, c=None, alpha=1, beta=0, transa=False, transb=False):
     equals scipy's ``A @ B`` bit for bit; so do ``transa=True`` and a CSC operand against scipy's
     ``A.T @ B`` / ``A @ B`` (the transpose is spg_csr2csc's stable counting sort, as in scipy).
     """
-    from .sparse import coo_matrix, csc_matrix
-    if not check_availability("spmm"):
-        raise RuntimeError("spmm is not available.")
-    if isinstance(a, csc_matrix):
-        a = a.T
-        transa = not transa
-    if not isinstance(a, (csr_matrix, coo_matrix)):
-        raise TypeError("unsupported type (actual: {})".format(type(a)))
-    if isinstance(a, coo_matrix):
-        a = a.tocsr()
+    a, transa = _sparse_operand("spmm", a, transa)
     if not isinstance(b, torch.Tensor):
         b = torch.from_numpy(np.asarray(b))
     assert a.ndim == b.ndim == 2
@@ -506,10 +575,7 @@ def spmm(a, b, c=None, alpha=1, beta=0, transa=False, transb=False):
     assert a.has_canonical_format
     dev = a.device
     m, n = a_shape[0], b.shape[1]
-    dt = np.promote_types(a.dtype, np.dtype(str(b.dtype).replace("torch.", "")))
-    if dt not in (np.float32, np.float64, np.complex64, np.complex128):
-        raise TypeError(f"spmm supports float32/float64/complex64/complex128, got {dt}")
-    a = a.astype(dt)
+    a = _promoted("spmm", a, b.dtype)
     tdt = a.data.dtype
     b = b.to(device=dev, dtype=tdt)
     lc = None
@@ -544,10 +610,27 @@ def spmm(a, b, c=None, alpha=1, beta=0, transa=False, transb=False):
     return c
 
 
+# has_*: True when the loaded library exports the operation's entry points (added within 0.2.0:
+# an older development build lacks them, and the containers then keep their torch form)
+
 def has_csr2csc() -> bool:
-    """True when the loaded library exports spg_csr2csc (added within 0.2.0: an older
-    development build lacks it, and the containers then keep their torch conversion)."""
-    return hasattr(_lib.load(), "spg_csr2csc")
+    return _lib.exports(*_lib.CSR2CSC)
+
+
+def has_csrgeam() -> bool:
+    return _lib.exports(*_lib.CSRGEAM)
+
+
+def has_canonicalize() -> bool:
+    return _lib.exports(*_lib.CANONICALIZE)
+
+
+def has_extract() -> bool:
+    return _lib.exports(*_lib.EXTRACT)
+
+
+def has_dense_convert() -> bool:
+    return _lib.exports(*_lib.DENSE_CONVERT)
 
 
 def _csr2csc_arrays(data, indices, indptr, rows: int, cols: int):
@@ -555,25 +638,21 @@ def _csr2csc_arrays(data, indices, indptr, rows: int, cols: int):
     the CSC arrays of the same matrix.  indptr comes back int32 whenever nnz fits."""
     dev = data.device
     nnz = int(data.numel())
-    ipd = torch.int32 if nnz <= 2 ** 31 - 1 else torch.int64
+    ipd = _indptr_dtype(nnz)
     out_data = torch.empty(nnz, dtype=data.dtype, device=dev)
     out_indices = torch.empty(nnz, dtype=torch.int32, device=dev)
     if nnz == 0:         # the reference fills zeros without a call (cusparse.py:1023-1024)
         return out_data, out_indices, torch.zeros(cols + 1, dtype=ipd, device=dev)
     data, indices, indptr = data.contiguous(), indices.contiguous(), indptr.to(ipd).contiguous()
     out_indptr = torch.empty(cols + 1, dtype=ipd, device=dev)
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _lib.get_handle(idx)
-    h.set_stream(_current_stream_ptr(idx))
-    va = SpgCsr(rows, cols, nnz, indptr.data_ptr(), indices.data_ptr(), data.data_ptr(), _IT[ipd], _VT[data.dtype])
-    vt = SpgCsr(cols, rows, nnz, out_indptr.data_ptr(), out_indices.data_ptr(), out_data.data_ptr(), _IT[ipd],
-                _VT[data.dtype])
-    ws_bytes = ctypes.c_size_t(0)
-    check(h.lib.spg_csr2csc(h.ptr, ctypes.byref(va), ctypes.byref(vt), ctypes.byref(ws_bytes), None), "spg_csr2csc")
-    # workspace from torch's caching allocator on the current stream, as in _spgemm
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    check(h.lib.spg_csr2csc(h.ptr, ctypes.byref(va), ctypes.byref(vt), ctypes.byref(ws_bytes),
-                            ctypes.c_void_p(ws.data_ptr())), "spg_csr2csc")
+    h = _handle_on(dev)
+    va = _view(rows, cols, nnz, indptr, indices, data, data.dtype)
+    vt = _view(cols, rows, nnz, out_indptr, out_indices, out_data, data.dtype)
+
+    def call(ws_bytes, ws):
+        return h.lib.spg_csr2csc(h.ptr, ctypes.byref(va), ctypes.byref(vt), ws_bytes, ws)
+    ws, ws_bytes, wp = _sized_workspace(call, "spg_csr2csc", dev)
+    check(call(ctypes.byref(ws_bytes), wp), "spg_csr2csc")
     return out_data, out_indices, out_indptr
 
 
@@ -582,13 +661,7 @@ def csr2csc(x):
     (modify_src/cupy-src/cupyx/cusparse.py:1014-1035), on ``spg_csr2csc``.  Stable: every
     column keeps x's stored entry order, so the arrays equal scipy's ``tocsc()`` array for array
     (duplicates kept), and the values are moved bit for bit."""
-    from .sparse import csc_matrix
-    if not check_availability("csr2csc"):
-        raise RuntimeError("csr2csc is not available.")
-    if not isinstance(x, csr_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError("csr2csc needs device-resident operands")
+    _guard("csr2csc", x, csr_matrix)
     m, n = x.shape
     data, indices, indptr = _csr2csc_arrays(x.data, x.indices, x.indptr, m, n)
     return csc_matrix((data, indices, indptr), shape=x.shape, canonical=True if x._canonical is True else None)
@@ -598,23 +671,29 @@ def csc2csr(x):
     """CSC -> CSR of the same matrix -- the drop-in for ``cupyx.cusparse.csc2csr``
     (modify_src/cupy-src/cupyx/cusparse.py:1092-1113): spg_csr2csc on the CSC arrays read as
     the CSR of the transpose.  Equals scipy's ``tocsr()`` array for array."""
-    from .sparse import csc_matrix
     if not check_availability("csc2csr"):
-        raise RuntimeError("csr2csc is not available.")
-    if not isinstance(x, csc_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError("csc2csr needs device-resident operands")
+        raise RuntimeError("csr2csc is not available.")   # (it has always named csr2csc)
+    _check_type(x, csc_matrix)
+    _check_device(x, "csc2csr")
     m, n = x.shape
     data, indices, indptr = _csr2csc_arrays(x.data, x.indices, x.indptr, n, m)
     return csr_matrix._from_parts(data, indices, indptr, (m, n), canonical=True if x._canonical is True else None)
 
 
-def has_csrgeam() -> bool:
-    """True when the loaded library exports spg_csrgeam (added within 0.2.0: an older
-    development build lacks it, and the containers then keep their torch addition)."""
-    lib = _lib.load()
-    return hasattr(lib, "spg_csrgeam_nnz") and hasattr(lib, "spg_csrgeam")
+def _csrgeam_arrays(ax, aj, ap, bx, bj, bp, shape, alpha, beta):
+    """(data, indices, indptr) of alpha * A + beta * B for the CSR arrays of two canonical
+    matrices of one shape and value type, on spg_csrgeam_nnz + spg_csrgeam."""
+    dev, dt = ax.device, ax.dtype
+    m, n = shape
+    na, nb = int(ax.numel()), int(bx.numel())
+    # nnz(C) <= nnz(A) + nnz(B): int32 row pointers whenever that bound fits, so no retry
+    ipd = _indptr_dtype(na + nb)
+    h = _handle_on(dev)
+    ap, bp = ap.to(ipd).contiguous(), bp.to(ipd).contiguous()
+    aj, ax, bj, bx = aj.contiguous(), ax.contiguous(), bj.contiguous(), bx.contiguous()
+    va, vb = ctypes.byref(_view(m, n, na, ap, aj, ax, dt)), ctypes.byref(_view(m, n, nb, bp, bj, bx, dt))
+    return _two_phase(h, ("spg_csrgeam_nnz", "spg_csrgeam"), (va, vb), lambda: (
+        ctypes.byref(_alpha_of(dt, alpha)), va, ctypes.byref(_alpha_of(dt, beta)), vb), m, n, dt, (ipd,), dev)
 
 
 def csrgeam2(a, b, alpha=1, beta=1):
@@ -632,59 +711,21 @@ def csrgeam2(a, b, alpha=1, beta=1):
         csr_matrix: C, canonical; its structure is the union of the two patterns (an entry that
         cancels stays as an explicit 0) and its values equal scipy's after dropping exact zeros.
     """
-    if not check_availability("csrgeam2"):
-        raise RuntimeError("csrgeam2 is not available.")
-    if not isinstance(a, csr_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(a)))
-    if not isinstance(b, csr_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(b)))
+    _guard("csrgeam2")
+    _check_type(a, csr_matrix)
+    _check_type(b, csr_matrix)
     assert a.has_canonical_format
     assert b.has_canonical_format
     if a.shape != b.shape:
         raise ValueError("inconsistent shapes")
     if a.device.type != "cuda" or b.device != a.device:
         raise RuntimeError("csrgeam2 needs device-resident operands on one device")
-    m, n = a.shape
     a, b = _cast_common_type(a, b)
-    dev, dt = a.device, a.data.dtype
-    # nnz(C) <= nnz(A) + nnz(B): int32 row pointers whenever that bound fits, so no retry
-    ipd = torch.int32 if a.nnz + b.nnz <= 2 ** 31 - 1 else torch.int64
-    h = _handle_for(a)
-    ap, bp = a.indptr.to(ipd).contiguous(), b.indptr.to(ipd).contiguous()
-    aj, ax, bj, bx = a.indices.contiguous(), a.data.contiguous(), b.indices.contiguous(), b.data.contiguous()
-    va = SpgCsr(m, n, a.nnz, ap.data_ptr(), aj.data_ptr() if a.nnz else 0, ax.data_ptr() if a.nnz else 0,
-                _IT[ipd], _VT[dt])
-    vb = SpgCsr(m, n, b.nnz, bp.data_ptr(), bj.data_ptr() if b.nnz else 0, bx.data_ptr() if b.nnz else 0,
-                _IT[ipd], _VT[dt])
-    c_indptr = torch.empty(m + 1, dtype=ipd, device=dev)
-    nnz = ctypes.c_int64(0)
-    ws_bytes = ctypes.c_size_t(0)
-    check(h.lib.spg_csrgeam_nnz(h.ptr, ctypes.byref(va), ctypes.byref(vb), None, _IT[ipd], ctypes.byref(nnz),
-                                ctypes.byref(ws_bytes), None), "spg_csrgeam_nnz")
-    # workspace from torch's caching allocator on the current stream, as in _spgemm
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    check(h.lib.spg_csrgeam_nnz(h.ptr, ctypes.byref(va), ctypes.byref(vb), ctypes.c_void_p(c_indptr.data_ptr()),
-                                _IT[ipd], ctypes.byref(nnz), ctypes.byref(ws_bytes),
-                                ctypes.c_void_p(ws.data_ptr())), "spg_csrgeam_nnz")
-    nnzc = int(nnz.value)
-    c_indices = torch.empty(nnzc, dtype=torch.int32, device=dev)
-    c_data = torch.empty(nnzc, dtype=dt, device=dev)
-    vc = SpgCsr(m, n, nnzc, c_indptr.data_ptr(), c_indices.data_ptr() if nnzc else 0,
-                c_data.data_ptr() if nnzc else 0, _IT[ipd], _VT[dt])
-    al, be = _alpha_of(dt, alpha), _alpha_of(dt, beta)
-    check(h.lib.spg_csrgeam(h.ptr, ctypes.byref(al), ctypes.byref(va), ctypes.byref(be), ctypes.byref(vb),
-                            ctypes.byref(vc), ws_bytes, ctypes.c_void_p(ws.data_ptr())), "spg_csrgeam")
-    return csr_matrix._from_parts(c_data, c_indices, c_indptr, (m, n), canonical=True)
+    parts = _csrgeam_arrays(a.data, a.indices, a.indptr, b.data, b.indices, b.indptr, a.shape, alpha, beta)
+    return csr_matrix._from_parts(*parts, a.shape, canonical=True)
 
 
 csrgeam = csrgeam2
-
-
-def has_canonicalize() -> bool:
-    """True when the loaded library exports spg_canonicalize (added within 0.2.0: an older
-    development build lacks it, and the containers then keep their torch canonicalisation)."""
-    lib = _lib.load()
-    return hasattr(lib, "spg_canonicalize_nnz") and hasattr(lib, "spg_canonicalize")
 
 
 def _canonicalize_arrays(data, indices, indptr, coo_rows, shape, ops: int, indptr_dtype=None):
@@ -695,40 +736,22 @@ def _canonicalize_arrays(data, indices, indptr, coo_rows, shape, ops: int, indpt
     dev, dt = data.device, data.dtype
     m, n = int(shape[0]), int(shape[1])
     nnz = int(data.numel())
-    ipd = torch.int32 if nnz <= 2 ** 31 - 1 else torch.int64
+    ipd = _indptr_dtype(nnz)
     cpd = indptr_dtype or ipd
     if nnz == 0:
         return (torch.empty(0, dtype=dt, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
                 torch.zeros(m + 1, dtype=cpd, device=dev))
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _lib.get_handle(idx)
-    h.set_stream(_current_stream_ptr(idx))
+    h = _handle_on(dev)
     data, indices = data.contiguous(), indices.to(torch.int32).contiguous()
     if coo_rows is not None:
-        coo_rows = coo_rows.to(torch.int32).contiguous()
+        coo_rows, indptr = coo_rows.to(torch.int32).contiguous(), None
     else:
         indptr = indptr.to(ipd).contiguous()
-    va = SpgCsr(m, n, nnz, 0 if coo_rows is not None else indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
-                _IT[ipd], _VT[dt])
+    va = _view(m, n, nnz, indptr, indices, data, dt, ipd)
     rows_p = ctypes.c_void_p(coo_rows.data_ptr()) if coo_rows is not None else None
-    c_indptr = torch.empty(m + 1, dtype=cpd, device=dev)
-    nnzc = ctypes.c_int64(0)
-    ws_bytes = ctypes.c_size_t(0)
-    check(h.lib.spg_canonicalize_nnz(h.ptr, ctypes.byref(va), rows_p, ops, None, _IT[cpd], ctypes.byref(nnzc),
-                                     ctypes.byref(ws_bytes), None), "spg_canonicalize_nnz")
-    # workspace from torch's caching allocator on the current stream, as in _spgemm
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    check(h.lib.spg_canonicalize_nnz(h.ptr, ctypes.byref(va), rows_p, ops, ctypes.c_void_p(c_indptr.data_ptr()),
-                                     _IT[cpd], ctypes.byref(nnzc), ctypes.byref(ws_bytes),
-                                     ctypes.c_void_p(ws.data_ptr())), "spg_canonicalize_nnz")
-    nc = int(nnzc.value)
-    c_indices = torch.empty(nc, dtype=torch.int32, device=dev)
-    c_data = torch.empty(nc, dtype=dt, device=dev)
-    vc = SpgCsr(m, n, nc, c_indptr.data_ptr(), c_indices.data_ptr() if nc else 0, c_data.data_ptr() if nc else 0,
-                _IT[cpd], _VT[dt])
-    check(h.lib.spg_canonicalize(h.ptr, ctypes.byref(va), rows_p, ops, ctypes.byref(vc), ws_bytes,
-                                 ctypes.c_void_p(ws.data_ptr())), "spg_canonicalize")
-    return c_data, c_indices, c_indptr
+    args = (ctypes.byref(va), rows_p, ops)
+    # one row-pointer type, the caller's: an OVERFLOW raises
+    return _two_phase(h, ("spg_canonicalize_nnz", "spg_canonicalize"), args, args, m, n, dt, (cpd,), dev)
 
 
 def canonicalize(x, sort=True, sum_duplicates=True, eliminate_zeros=False):
@@ -739,13 +762,7 @@ def canonicalize(x, sort=True, sum_duplicates=True, eliminate_zeros=False):
     ``coo2csr`` (modify_src/cupy-src/cupyx/cusparse.py:832-984), ``sum_duplicates`` and
     ``eliminate_zeros``, in one pass over ``spg_canonicalize_nnz`` + ``spg_canonicalize``.  The
     result is flagged canonical when duplicates were summed."""
-    from .sparse import coo_matrix
-    if not check_availability("canonicalize"):
-        raise RuntimeError("canonicalize is not available.")
-    if not isinstance(x, (csr_matrix, coo_matrix)):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError("canonicalize needs device-resident operands")
+    _guard("canonicalize", x, (csr_matrix, coo_matrix))
     ops = ((_lib.SPG_CANON_SORT if sort else 0) | (_lib.SPG_CANON_SUM if sum_duplicates else 0) |
            (_lib.SPG_CANON_DROP_ZEROS if eliminate_zeros else 0))
     if isinstance(x, coo_matrix):
@@ -763,24 +780,12 @@ def csrsort(x):
     """Sorts the indices of every row of ``x`` in place, stably, duplicates kept -- the drop-in
     for ``cupyx.cusparse.csrsort`` (modify_src/cupy-src/cupyx/cusparse.py:832-867), on
     ``spg_canonicalize`` with SPG_CANON_SORT."""
-    if not check_availability("csrsort"):
-        raise RuntimeError("csrsort is not available.")
-    if not isinstance(x, csr_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError("csrsort needs device-resident operands")
+    _guard("csrsort", x, csr_matrix)
     if x._canonical is True:
         return
     x.data, x.indices, _ = _canonicalize_arrays(x.data, x.indices, x.indptr, None, x.shape, _lib.SPG_CANON_SORT,
                                                 x.indptr.dtype)
     x._canonical = None   # sorted now; canonical when it holds no duplicates
-
-
-def has_extract() -> bool:
-    """True when the loaded library exports spg_csr_extract (added within 0.2.0: an older
-    development build lacks it, and the containers then keep their torch indexing)."""
-    lib = _lib.load()
-    return hasattr(lib, "spg_csr_extract_nnz") and hasattr(lib, "spg_csr_extract")
 
 
 def _sel_view(sel):
@@ -804,43 +809,17 @@ def _extract_arrays(data, indices, indptr, shape, rows_sel, cols_sel):
     dev, dt = data.device, data.dtype
     m, n = int(shape[0]), int(shape[1])
     nnz = int(data.numel())
-    ipd = torch.int32 if nnz <= 2 ** 31 - 1 else torch.int64
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _lib.get_handle(idx)
-    h.set_stream(_current_stream_ptr(idx))
+    ipd = _indptr_dtype(nnz)
+    h = _handle_on(dev)
     data, indices, indptr = data.contiguous(), indices.to(torch.int32).contiguous(), indptr.to(ipd).contiguous()
-    va = SpgCsr(m, n, nnz, indptr.data_ptr(), indices.data_ptr() if nnz else 0, data.data_ptr() if nnz else 0,
-                _IT[ipd], _VT[dt])
-    rp, rkeep = _sel_view(rows_sel)
+    va = _view(m, n, nnz, indptr, indices, data, dt)
+    rp, rkeep = _sel_view(rows_sel)   # (rkeep, ckeep: the selections' memory, held until the return)
     cp, ckeep = _sel_view(cols_sel)
     nr = m if rows_sel is None else rows_sel[2] if isinstance(rows_sel, tuple) else int(rows_sel.numel())
     nc = n if cols_sel is None else cols_sel[2] if isinstance(cols_sel, tuple) else int(cols_sel.numel())
-    nnzc = ctypes.c_int64(0)
-    ws_bytes = ctypes.c_size_t(0)
-    check(h.lib.spg_csr_extract_nnz(h.ptr, ctypes.byref(va), rp, cp, None, _IT[torch.int32], ctypes.byref(nnzc),
-                                    ctypes.byref(ws_bytes), None), "spg_csr_extract_nnz")
-    # workspace from torch's caching allocator on the current stream, as in _spgemm
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    cpd = torch.int32
-    c_indptr = torch.empty(nr + 1, dtype=cpd, device=dev)
-    st = h.lib.spg_csr_extract_nnz(h.ptr, ctypes.byref(va), rp, cp, ctypes.c_void_p(c_indptr.data_ptr()), _IT[cpd],
-                                   ctypes.byref(nnzc), ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()))
-    if st == _lib.STATUS_OVERFLOW:   # nnz(C) past int32: the same pass into an int64 row pointer
-        cpd = torch.int64
-        c_indptr = torch.empty(nr + 1, dtype=cpd, device=dev)
-        st = h.lib.spg_csr_extract_nnz(h.ptr, ctypes.byref(va), rp, cp, ctypes.c_void_p(c_indptr.data_ptr()),
-                                       _IT[cpd], ctypes.byref(nnzc), ctypes.byref(ws_bytes),
-                                       ctypes.c_void_p(ws.data_ptr()))
-    check(st, "spg_csr_extract_nnz")
-    nz = int(nnzc.value)
-    c_indices = torch.empty(nz, dtype=torch.int32, device=dev)
-    c_data = torch.empty(nz, dtype=dt, device=dev)
-    vc = SpgCsr(nr, nc, nz, c_indptr.data_ptr(), c_indices.data_ptr() if nz else 0, c_data.data_ptr() if nz else 0,
-                _IT[cpd], _VT[dt])
-    check(h.lib.spg_csr_extract(h.ptr, ctypes.byref(va), rp, cp, ctypes.byref(vc), ws_bytes,
-                                ctypes.c_void_p(ws.data_ptr())), "spg_csr_extract")
-    del rkeep, ckeep
-    return c_data, c_indices, c_indptr
+    args = (ctypes.byref(va), rp, cp)
+    return _two_phase(h, ("spg_csr_extract_nnz", "spg_csr_extract"), args, args, nr, nc, dt,
+                      (torch.int32, torch.int64), dev)
 
 
 def extract(x, rows=None, cols=None):
@@ -852,29 +831,9 @@ def extract(x, rows=None, cols=None):
     always one selection per axis (outer indexing), also when both are lists.  Rows keep their
     stored entry order and values are moved bit for bit; the arrays equal scipy's array for array
     wherever the column list has no repeat (repeats come in ascending list position)."""
-    from .sparse import _axis_selector, csc_matrix
-    if not check_availability("extract"):
-        raise RuntimeError("extract is not available.")
-    if not isinstance(x, (csr_matrix, csc_matrix)):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError("extract needs device-resident operands")
+    _guard("extract", x, (csr_matrix, csc_matrix))
     m, n = x.shape
     return x._extract(_axis_selector(rows, m, x.device), _axis_selector(cols, n, x.device))
-
-
-def has_dense_convert() -> bool:
-    """True when the loaded library exports spg_csr2dense and spg_dense2csr (added within 0.2.0:
-    an older development build lacks them, and the containers then keep their torch form)."""
-    lib = _lib.load()
-    return all(hasattr(lib, n) for n in ("spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr"))
-
-
-def _handle_on(dev) -> _lib.Handle:
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    h = _lib.get_handle(idx)
-    h.set_stream(_current_stream_ptr(idx))
-    return h
 
 
 def _new_dense(m: int, n: int, dtype, dev, order: str) -> torch.Tensor:
@@ -907,19 +866,13 @@ def _todense_into(data, indices, indptr, rows: int, cols: int, view: torch.Tenso
     if ipd == torch.int32 and nnz > 2 ** 31 - 1:
         ipd = torch.int64
     indptr, indices, data = indptr.to(ipd).contiguous(), indices.to(torch.int32).contiguous(), data.contiguous()
-    va = SpgCsr(rows, cols, nnz, indptr.data_ptr(), indices.data_ptr() if nnz else 0,
-                data.data_ptr() if nnz else 0, _IT[ipd], _VT[data.dtype])
+    va = _view(rows, cols, nnz, indptr, indices, data, data.dtype)
     vd = _dense_view(view, *_dense_layout(view))
     check(h.lib.spg_csr2dense(h.ptr, ctypes.byref(va), ctypes.byref(vd)), "spg_csr2dense")
 
 
 def _compressed2dense(x, kind, name: str, out, order: str) -> torch.Tensor:
-    if not check_availability(name):
-        raise RuntimeError(f"{name} is not available.")
-    if not isinstance(x, kind):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError(f"{name} needs device-resident operands")
+    _guard(name, x, kind)
     m, n = x.shape
     out = _new_dense(m, n, x.data.dtype, x.device, order) if out is None else \
         _check_out(out, m, n, x.data.dtype, x.device)
@@ -944,7 +897,6 @@ def csc2dense(x, out=None, order="C"):
     """The CSC matrix ``x`` as a dense 2-D tensor -- the drop-in for ``cupyx.cusparse.csc2dense``
     (modify_src/cupy-src/cupyx/cusparse.py:800-829): ``spg_csr2dense`` on the CSC arrays read as
     the CSR of the transpose, into the transposed view of the result; no transpose is made."""
-    from .sparse import csc_matrix
     return _compressed2dense(x, csc_matrix, "csc2dense", out, order)
 
 
@@ -953,17 +905,13 @@ def sparseToDense(x, out=None):
     ``cupyx.cusparse.sparseToDense`` (modify_src/cupy-src/cupyx/cusparse.py:1805-1833).  COO
     entries are grouped by row first, stably (spg_canonicalize with no op), so duplicates are
     still added in stored order."""
-    from .sparse import coo_matrix, csc_matrix
-    if not check_availability("sparseToDense"):
-        raise RuntimeError("sparseToDense is not available.")
+    _guard("sparseToDense")
     if isinstance(x, csr_matrix):
         return csr2dense(x, out=out)
     if isinstance(x, csc_matrix):
         return csc2dense(x, out=out)
-    if not isinstance(x, coo_matrix):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
-    if x.device.type != "cuda":
-        raise RuntimeError("sparseToDense needs device-resident operands")
+    _check_type(x, coo_matrix)
+    _check_device(x, "sparseToDense")
     m, n = x.shape
     out = _new_dense(m, n, x.data.dtype, x.device, "C") if out is None else \
         _check_out(out, m, n, x.data.dtype, x.device)
@@ -981,44 +929,18 @@ def _dense2csr_arrays(t: torch.Tensor):
         t = t.contiguous()
         lay = _dense_layout(t)
     h = _handle_on(dev)
-    vd = _dense_view(t, *lay)
-    ws_bytes = ctypes.c_size_t(0)
-    nnz = ctypes.c_int64(0)
-    check(h.lib.spg_dense2csr_nnz(h.ptr, ctypes.byref(vd), None, _lib.SPG_INDEX_32I, ctypes.byref(nnz),
-                                  ctypes.byref(ws_bytes), None), "spg_dense2csr_nnz")
-    # workspace from torch's caching allocator on the current stream, as in _spgemm
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=dev)
-    ipd = torch.int32
-    c_indptr = torch.empty(m + 1, dtype=ipd, device=dev)
-    st = h.lib.spg_dense2csr_nnz(h.ptr, ctypes.byref(vd), ctypes.c_void_p(c_indptr.data_ptr()), _IT[ipd],
-                                 ctypes.byref(nnz), ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()))
-    if st == _lib.STATUS_OVERFLOW:   # nnz >= 2**31: once more with int64 row pointers
-        ipd = torch.int64
-        c_indptr = torch.empty(m + 1, dtype=ipd, device=dev)
-        st = h.lib.spg_dense2csr_nnz(h.ptr, ctypes.byref(vd), ctypes.c_void_p(c_indptr.data_ptr()), _IT[ipd],
-                                     ctypes.byref(nnz), ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()))
-    check(st, "spg_dense2csr_nnz")
-    nc = int(nnz.value)
-    c_indices = torch.empty(nc, dtype=torch.int32, device=dev)
-    c_data = torch.empty(nc, dtype=dt, device=dev)
-    vc = SpgCsr(m, n, nc, c_indptr.data_ptr(), c_indices.data_ptr() if nc else 0, c_data.data_ptr() if nc else 0,
-                _IT[ipd], _VT[dt])
-    check(h.lib.spg_dense2csr(h.ptr, ctypes.byref(vd), ctypes.byref(vc), ws_bytes, ctypes.c_void_p(ws.data_ptr())),
-          "spg_dense2csr")
-    return c_data, c_indices, c_indptr
+    vd = (ctypes.byref(_dense_view(t, *lay)),)
+    return _two_phase(h, ("spg_dense2csr_nnz", "spg_dense2csr"), vd, vd, m, n, dt, (torch.int32, torch.int64), dev)
 
 
 def _check_dense_operand(x, name: str) -> torch.Tensor:
-    if not check_availability(name):
-        raise RuntimeError(f"{name} is not available.")
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("unsupported type (actual: {})".format(type(x)))
+    _guard(name)
+    _check_type(x, torch.Tensor)
     if x.ndim != 2:
         raise ValueError("expected a 2-D tensor")
     if x.dtype not in _VT:
         raise TypeError(f"{name} supports float32/float64/complex64/complex128, got {x.dtype}")
-    if x.device.type != "cuda":
-        raise RuntimeError(f"{name} needs device-resident operands")
+    _check_device(x, name)
     return x
 
 
@@ -1036,7 +958,6 @@ def dense2csc(x):
     """The 2-D device tensor ``x`` as a canonical csc_matrix -- the drop-in for
     ``cupyx.cusparse.dense2csc`` (modify_src/cupy-src/cupyx/cusparse.py:1146-1185): the CSR
     conversion of the transposed view, which moves no data."""
-    from .sparse import csc_matrix
     x = _check_dense_operand(x, "dense2csc")
     return csc_matrix(_dense2csr_arrays(x.t()), shape=x.shape, canonical=True)
 
@@ -1044,7 +965,6 @@ def dense2csc(x):
 def denseToSparse(x, format="csr"):
     """``x`` as a csr_matrix, csc_matrix or coo_matrix -- the drop-in for
     ``cupyx.cusparse.denseToSparse`` (modify_src/cupy-src/cupyx/cusparse.py:1733-1802)."""
-    from .sparse import coo_matrix
     if format == "csr":
         return dense2csr(x)
     if format == "csc":
@@ -1058,37 +978,20 @@ def denseToSparse(x, format="csr"):
 def num_products(a: csr_matrix, b: csr_matrix) -> int:
     """P = number of scalar products of A.B (cusparseSpGEMM_getNumProducts); GFLOPS = 2P/t."""
     h = _handle_for(a)
-    va, vb = _csr_view(a), _csr_view(b)
-    ws_bytes = ctypes.c_size_t(0)
-    check(h.lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), _lib.SPG_ALG2, 0.2,
-                         ctypes.byref(ws_bytes), None, None), "spg_plan")
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=a.device)
-    plan = ctypes.c_void_p()
-    check(h.lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), _lib.SPG_ALG2, 0.2,
-                         ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()),
-                         ctypes.byref(plan)), "spg_plan")
-    try:
+    with _planned(h, a, b, _lib.SPG_ALG2, 0.2) as (plan, _):
         p = ctypes.c_int64(0)
         check(h.lib.spg_num_products(h.ptr, plan, ctypes.byref(p)), "spg_num_products")
         return int(p.value)
-    finally:
-        h.lib.spg_plan_destroy(plan)
 
 
 def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float = 0.2) -> dict:
     """What spgemm(a, b, alg, chunk_fraction) runs (spg_plan_info): the kernel path, the
     tile geometry and the row chunks (ALG3's chunk cut).  A diagnostic for tests/profilers."""
     h = _handle_for(a)
-    va, vb = _csr_view(a), _csr_view(b)
-    algo = _ALG.get(alg, _lib.SPG_ALG_DEFAULT)
-    ws_bytes = ctypes.c_size_t(0)
-    check(h.lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, float(chunk_fraction),
-                         ctypes.byref(ws_bytes), None, None), "spg_plan")
-    ws = torch.empty(max(ws_bytes.value, 1), dtype=torch.uint8, device=a.device)
-    plan = ctypes.c_void_p()
-    check(h.lib.spg_plan(h.ptr, ctypes.byref(va), ctypes.byref(vb), algo, float(chunk_fraction),
-                         ctypes.byref(ws_bytes), ctypes.c_void_p(ws.data_ptr()), ctypes.byref(plan)), "spg_plan")
-    try:
+    with contextlib.ExitStack() as after, \
+            _planned(h, a, b, _ALG.get(alg, _lib.SPG_ALG_DEFAULT), float(chunk_fraction)) as (plan, _):
+        # (once there is a plan: the stream is synchronised after the plan is destroyed)
+        after.callback(lambda: torch.cuda.current_stream(a.device).synchronize())
         info = _lib.SpgPlanInfo()
         check(h.lib.spg_plan_info(plan, ctypes.byref(info), None, 0), "spg_plan_info")
         rows = (ctypes.c_int64 * (info.n_chunks + 1))()
@@ -1097,9 +1000,6 @@ def plan_info(a: csr_matrix, b: csr_matrix, alg: int = 0, chunk_fraction: float 
                 "tiles_per_row": info.tiles_per_row, "dense_tiles": bool(info.dense_tiles),
                 "lds_ordered": bool(info.lds_ordered), "record_group": int(info.record_group),
                 "chunk_rows": [int(x) for x in rows]}
-    finally:
-        h.lib.spg_plan_destroy(plan)
-        torch.cuda.current_stream(a.device).synchronize()
 
 
 __all__ = ["spgemm", "spmv", "spmm", "csr2csc", "csc2csr", "csrgeam2", "csrgeam", "canonicalize", "csrsort",

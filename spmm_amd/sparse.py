@@ -35,12 +35,19 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _lib
+
 _TORCH_OF = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
              np.dtype(np.complex64): torch.complex64, np.dtype(np.complex128): torch.complex128,
              np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}
 _NP_OF = {v: k for k, v in _TORCH_OF.items()}
 
 INT32_MAX = 2 ** 31 - 1
+
+
+def _indptr_dtype(nnz: int) -> torch.dtype:
+    """int32 row pointers while the entry count fits (CuPy's type), int64 beyond."""
+    return torch.int32 if nnz <= INT32_MAX else torch.int64
 
 
 def _as_tensor(x, dtype: torch.dtype, device) -> torch.Tensor:
@@ -54,13 +61,11 @@ def _default_device():
         else torch.device("cpu")
 
 
-def _engine_transposes(t: torch.Tensor) -> bool:
-    """CSR <-> CSC of these tensors runs on spg_csr2csc: they sit on a GPU and the loaded
-    library exports the symbol (otherwise the torch conversion serves)."""
-    if t.device.type != "cuda":
-        return False
-    from . import cusparse
-    return cusparse.has_csr2csc()
+def _engine_has(t: torch.Tensor, symbols, extent: int = 0) -> bool:
+    """An operation on these tensors runs in the engine: they sit on a GPU, `extent` (where the
+    engine keeps that axis in int32 ids) fits, and the loaded library exports the operation's
+    symbols (otherwise the torch form of the same rule serves)."""
+    return t.device.type == "cuda" and extent <= INT32_MAX and _lib.exports(*symbols)
 
 
 def _stable_by_index(data, indices, indptr, n_major: int, n_minor: int):
@@ -72,34 +77,6 @@ def _stable_by_index(data, indices, indptr, n_major: int, n_minor: int):
     ipd = torch.int32 if data.numel() <= INT32_MAX else torch.int64
     return (data[order].contiguous(), major[order].to(torch.int32),
             _indptr_from_rows(indices.to(torch.int64), n_minor, ipd))
-
-
-def _engine_adds(t: torch.Tensor) -> bool:
-    """A + B of these tensors runs on spg_csrgeam: they sit on a GPU and the loaded library
-    exports the symbols (otherwise the torch addition serves)."""
-    if t.device.type != "cuda":
-        return False
-    from . import cusparse
-    return cusparse.has_csrgeam()
-
-
-def _engine_canonicalizes(t: torch.Tensor, shape) -> bool:
-    """Sorting, duplicate summing, zero dropping and COO -> CSR of these tensors run on
-    spg_canonicalize: they sit on a GPU, both extents fit the engine's int32 row and column ids
-    and the loaded library exports the symbols (otherwise the torch form of the same rule serves)."""
-    if t.device.type != "cuda" or max(shape) > INT32_MAX:
-        return False
-    from . import cusparse
-    return cusparse.has_canonicalize()
-
-
-def _engine_converts_dense(t: torch.Tensor) -> bool:
-    """Dense <-> CSR of these tensors runs on spg_csr2dense / spg_dense2csr: they sit on a GPU
-    and the loaded library exports the symbols (otherwise the torch form of the same rules serves)."""
-    if t.device.type != "cuda":
-        return False
-    from . import cusparse
-    return cusparse.has_dense_convert()
 
 
 _VALUE_TYPES = (torch.float32, torch.float64, torch.complex64, torch.complex128)
@@ -127,7 +104,7 @@ def _dense_to_csr(t: torch.Tensor):
     """(data, indices, indptr) of scipy's csr_matrix(t) for a 2-D tensor: spg_dense2csr's rule
     (include/spgemm.h) -- an element is kept iff its bits without the sign(s) are nonzero, kept
     values are copied, columns ascend.  The engine for device tensors, torch ops otherwise."""
-    if _engine_converts_dense(t):
+    if _engine_has(t, _lib.DENSE_CONVERT):
         from . import cusparse
         return cusparse._dense2csr_arrays(t)
     m = int(t.shape[0])
@@ -138,7 +115,7 @@ def _dense_to_csr(t: torch.Tensor):
         keep = keep.any(dim=-1)
     nz = keep.nonzero()   # row-major: rows ascend, columns ascend inside a row
     rows, cols = nz[:, 0], nz[:, 1]
-    ipd = torch.int32 if rows.numel() <= INT32_MAX else torch.int64
+    ipd = _indptr_dtype(rows.numel())
     return t[rows, cols].contiguous(), cols.to(torch.int32), _indptr_from_rows(rows, m, ipd)
 
 
@@ -228,16 +205,6 @@ def _geam_torch(a: "csr_matrix", b: "csr_matrix", alpha, beta) -> "csr_matrix":
     ipd = torch.int32 if keys.numel() <= INT32_MAX else torch.int64
     return csr_matrix._from_parts(data, (keys - rows * max(n, 1)).to(torch.int32),
                                   _indptr_from_rows(rows, m, ipd), (m, n), canonical=True)
-
-
-def _engine_extracts(t: torch.Tensor, shape) -> bool:
-    """A[rows, cols] of these tensors runs on spg_csr_extract: they sit on a GPU, the minor
-    extent fits the engine's int32 column ids and the loaded library exports the symbols
-    (otherwise the torch form of the same rule serves)."""
-    if t.device.type != "cuda" or shape[1] > INT32_MAX:
-        return False
-    from . import cusparse
-    return cusparse.has_extract()
 
 
 def _is_int(x) -> bool:
@@ -343,7 +310,7 @@ def _extract_compressed(data, indices, indptr, n_major: int, n_minor: int, major
     """The selected major segments and minor indices of compressed arrays, with the canonical
     flag of the result: the source's when the minor axis is kept or cut by an ascending range,
     unknown (``None``: checked lazily) for a list or a descending range."""
-    if _engine_extracts(data, (n_major, n_minor)):
+    if _engine_has(data, _lib.EXTRACT, n_minor):
         from . import cusparse
         parts = cusparse._extract_arrays(data, indices, indptr, (n_major, n_minor), major_sel, minor_sel)
     else:
@@ -541,7 +508,7 @@ class csr_matrix(_Compressed):
             self.data = _as_tensor(data, _TORCH_OF[np.dtype(ddt)], device)
             self.indices = _as_tensor(indices, torch.int32, device)
             # int32 row pointers whenever they fit (CuPy casts to int32), int64 beyond
-            ipd = torch.int32 if self.data.numel() <= INT32_MAX else torch.int64
+            ipd = _indptr_dtype(self.data.numel())
             self.indptr = _as_tensor(indptr, ipd, device)
             self._shape = (int(shape[0]), int(shape[1]))
             self._canonical = canonical
@@ -551,7 +518,7 @@ class csr_matrix(_Compressed):
             if dtype is not None:
                 S = S.astype(dtype)
             canon = bool(S.has_canonical_format)
-            ipd = torch.int32 if S.nnz <= INT32_MAX else torch.int64
+            ipd = _indptr_dtype(S.nnz)
             self.data = _as_tensor(S.data, _TORCH_OF[np.dtype(S.dtype)], device)
             self.indices = _as_tensor(S.indices, torch.int32, device)
             self.indptr = _as_tensor(S.indptr, ipd, device)
@@ -607,8 +574,8 @@ class csr_matrix(_Compressed):
         if self._canonical is True or (self._canonical is None and self.has_canonical_format):
             return
         m, n = self._shape
-        if _engine_canonicalizes(self.data, self._shape):
-            from . import _lib, cusparse
+        if _engine_has(self.data, _lib.CANONICALIZE, max(self._shape)):
+            from . import cusparse
             self.data, self.indices, self.indptr = cusparse._canonicalize_arrays(
                 self.data, self.indices, self.indptr, None, self._shape, _lib.SPG_CANON_SUM, self.indptr.dtype)
             self._canonical = True
@@ -634,8 +601,8 @@ class csr_matrix(_Compressed):
     def eliminate_zeros(self) -> None:
         """Drop the stored entries that equal zero, in place, the stored order kept (cupyx
         _csr.py:288-302): spg_canonicalize for device tensors, else the torch form."""
-        if _engine_canonicalizes(self.data, self._shape):
-            from . import _lib, cusparse
+        if _engine_has(self.data, _lib.CANONICALIZE, max(self._shape)):
+            from . import cusparse
             self.data, self.indices, self.indptr = cusparse._canonicalize_arrays(
                 self.data, self.indices, self.indptr, None, self._shape, _lib.SPG_CANON_DROP_ZEROS,
                 self.indptr.dtype)
@@ -666,7 +633,7 @@ class csr_matrix(_Compressed):
         return self.copy() if copy else self
 
     def todense(self, order=None, out=None) -> torch.Tensor:
-        if _engine_converts_dense(self.data):
+        if _engine_has(self.data, _lib.DENSE_CONVERT):
             from . import cusparse
             if order not in (None, "C", "F"):
                 raise ValueError("order must be 'C' or 'F'")
@@ -707,7 +674,7 @@ class csr_matrix(_Compressed):
         self.sum_duplicates()
         other = other.tocsr()
         other.sum_duplicates()
-        if _engine_adds(self.data) and other.device == self.device:
+        if _engine_has(self.data, _lib.CSRGEAM) and other.device == self.device:
             from . import cusparse
             return cusparse.csrgeam2(self, other, alpha, beta)
         return _geam_torch(self, other, alpha, beta)
@@ -715,7 +682,7 @@ class csr_matrix(_Compressed):
     def tocsc(self, copy=False) -> "csc_matrix":
         """The same matrix in CSC, array for array what scipy's ``tocsc()`` gives (every
         column in stored entry order, duplicates kept): spg_csr2csc for device tensors."""
-        if _engine_transposes(self.data):
+        if _engine_has(self.data, _lib.CSR2CSC):
             from . import cusparse
             return cusparse.csr2csc(self)
         data, indices, indptr = _stable_by_index(self.data, self.indices, self.indptr, *self._shape)
@@ -742,7 +709,7 @@ class csr_matrix(_Compressed):
         canonical A^T; otherwise duplicates are then summed in stored order, as the torch path
         does), else through COO with rows and columns swapped."""
         m, n = self._shape
-        if _engine_transposes(self.data):
+        if _engine_has(self.data, _lib.CSR2CSC):
             from . import cusparse
             t = cusparse.csr2csc(self)
             out = csr_matrix._from_parts(t.data, t.indices, t.indptr, (n, m), canonical=t._canonical)
@@ -812,8 +779,8 @@ class coo_matrix(_SparseBase):
         _coo.py tocsr: sum_duplicates, then coo2csr): spg_canonicalize for device tensors, else
         the torch form of the same rule."""
         m, n = self._shape
-        if _engine_canonicalizes(self.data, self._shape):
-            from . import _lib, cusparse
+        if _engine_has(self.data, _lib.CANONICALIZE, max(self._shape)):
+            from . import cusparse
             data, indices, indptr = cusparse._canonicalize_arrays(self.data, self.col, None, self.row, self._shape,
                                                                   _lib.SPG_CANON_SUM)
             if indptr.dtype == torch.int64 and data.numel() <= INT32_MAX:
@@ -825,7 +792,7 @@ class coo_matrix(_SparseBase):
         uniq, counts = torch.unique_consecutive(key_s, return_counts=True)
         data_u = data_s if uniq.numel() == key_s.numel() else _segmented_sequential_sum(data_s, counts)
         urow = torch.div(uniq, max(n, 1), rounding_mode="floor")
-        ipd = torch.int32 if uniq.numel() <= INT32_MAX else torch.int64
+        ipd = _indptr_dtype(uniq.numel())
         return csr_matrix((data_u, (uniq - urow * max(n, 1)).to(torch.int32),
                            _indptr_from_rows(urow, m, ipd)), shape=(m, n), canonical=True)
 
@@ -844,7 +811,7 @@ class coo_matrix(_SparseBase):
         self.data, self.row, self.col = self.data[keep].contiguous(), self.row[keep], self.col[keep]
 
     def todense(self, order=None, out=None) -> torch.Tensor:
-        if _engine_converts_dense(self.data) and max(self._shape) <= INT32_MAX:
+        if _engine_has(self.data, _lib.DENSE_CONVERT) and max(self._shape) <= INT32_MAX:
             from . import cusparse
             d = cusparse.sparseToDense(self, out=out)
             return d if out is not None else _ordered(d, order, None)
@@ -852,7 +819,7 @@ class coo_matrix(_SparseBase):
         key = self.row * max(self._shape[1], 1) + self.col
         _, perm = torch.sort(key, stable=True)
         rows = self.row[perm]
-        ipd = torch.int32 if rows.numel() <= INT32_MAX else torch.int64
+        ipd = _indptr_dtype(rows.numel())
         return _ordered(_compressed_to_dense(self.data[perm], self.col[perm], _indptr_from_rows(
             rows, self._shape[0], ipd), *self._shape), order, out)
 
@@ -892,7 +859,7 @@ class csc_matrix(_Compressed):
             ddt = _NP_OF[data.dtype] if isinstance(data, torch.Tensor) else np.asarray(data).dtype
             self.data = _as_tensor(data, _TORCH_OF[np.dtype(ddt)], device)
             self.indices = _as_tensor(indices, torch.int32, device)
-            ipd = torch.int32 if self.data.numel() <= INT32_MAX else torch.int64
+            ipd = _indptr_dtype(self.data.numel())
             self.indptr = _as_tensor(indptr, ipd, device)
             self._shape = (int(shape[0]), int(shape[1]))
             self._canonical = canonical
@@ -921,7 +888,7 @@ class csc_matrix(_Compressed):
     def T(self) -> csr_matrix:
         """Transpose as CSR without data movement (CuPy returns csr for csc.T)."""
         m, n = self._shape
-        ipd = torch.int32 if self.nnz <= INT32_MAX else torch.int64
+        ipd = _indptr_dtype(self.nnz)
         return csr_matrix((self.data, self.indices, self.indptr.to(ipd)), shape=(n, m))
 
     def transpose(self, axes=None, copy=False) -> csr_matrix:
@@ -954,7 +921,7 @@ class csc_matrix(_Compressed):
         canonical CSR; otherwise duplicates are then summed in stored order, as the torch path
         does), else through COO."""
         m, n = self._shape
-        if _engine_transposes(self.data):
+        if _engine_has(self.data, _lib.CSR2CSC):
             from . import cusparse
             out = cusparse.csc2csr(self)
             out.sum_duplicates()
@@ -966,7 +933,7 @@ class csc_matrix(_Compressed):
 
     def todense(self, order=None, out=None) -> torch.Tensor:
         m, n = self._shape
-        if _engine_converts_dense(self.data):
+        if _engine_has(self.data, _lib.DENSE_CONVERT):
             from . import cusparse
             if order not in (None, "C", "F"):
                 raise ValueError("order must be 'C' or 'F'")
