@@ -293,6 +293,86 @@ spg_status_t spg_csrgeam(spg_handle_t handle, const void *alpha, const spg_csr_t
                          const void *beta, const spg_csr_t *B, spg_csr_t *C,
                          size_t workspace_bytes, void *workspace);
 
+/* Element-wise binary operations: C = op(A, B), op one of multiply, maximum, minimum, in two calls
+ * like the addition -- a structure pass that writes C's row pointer and returns nnz(C), then a
+ * value pass into the caller's C.  scipy's csr_binop_csr_canonical, behind A.multiply(B),
+ * A.maximum(B) and A.minimum(B).  (cupyx's csr_matrix.multiply and _maximum_minimum, which run
+ * kernels of their own and no cuSPARSE call: cupy-src/cupyx/scipy/sparse/_csr.py:328-342 and
+ * :297-326, with the kernels multiply_by_csr at :733-835 and binopt_csr at :880-945.  Added within
+ * 0.2.0: a caller detects it by symbol lookup.)
+ *   Inputs: A and B canonical CSR (sorted, duplicate-free rows) of the same shape, the same value
+ *     type and the same indptr type.  C's row pointer may be int32 or int64 whatever theirs is.
+ *   The rule: over the union of the two patterns, in ascending column order, r = op(a, b), where
+ *     an operand without the entry contributes +0 (+0+0i for complex); (column, r) is kept iff
+ *     r != 0.  The test is made on r's integer bits, as spg_dense2csr makes it (no float mode can
+ *     flush a denormal): +-0 is dropped; denormals, +-inf and NaN are kept; a complex r is dropped
+ *     only when both parts are +-0.  So C's structure depends on the values: inf * (missing) is
+ *     NaN and is stored, max(-2, missing) is 0 and is not.  C is canonical by construction and
+ *     equals scipy's result for indptr and indices array for array.
+ *   SPG_BINOP_MUL: a * b rounded once; complex (ac - bd) + (ad + bc)i, every product and sum
+ *     rounded on its own (no FMA), the products' rule.  No shortcut on a value: a one-sided entry
+ *     is still a * 0, so a finite one is dropped and an inf or NaN one is stored as NaN.
+ *   SPG_BINOP_MAX: (a < b) ? b : a.  max(NaN, x) is NaN, max(x, NaN) is x; max(-0.0, +0.0) is
+ *     -0.0 and is dropped.  A one-sided negative entry gives 0 and is dropped.
+ *   SPG_BINOP_MIN: (b < a) ? b : a.  A one-sided positive entry gives 0 and is dropped.
+ *   For complex values < is scipy's lexicographic order, x.re == y.re ? x.im < y.im : x.re < y.re.
+ *     MAX and MIN move one operand bit for bit.
+ *   Values follow the special-value rule above: +-0, denormals and +-inf bit for bit, NaN exactly
+ *     where scipy has one, NaN sign and payload unspecified.  Identical from run to run: no global
+ *     atomic places an entry, no position depends on the order in which anything landed.
+ *   spg_csr_binop_nnz, workspace == NULL: size query, *workspace_bytes is set by host arithmetic
+ *     and nothing is launched.  workspace != NULL: *workspace_bytes must be >= the queried size;
+ *     writes C_indptr (A->rows + 1 entries of C_indptr_type) and *nnzC, waiting for the device
+ *     once, for nnzC.  SPG_STATUS_OVERFLOW when nnzC does not fit an int32 C_indptr (*nnzC is
+ *     still set: call again with an int64 array).  Unlike spg_csrgeam_nnz this call READS A's and
+ *     B's values, and they must not change between the two calls (as with SPG_CANON_DROP_ZEROS):
+ *     the value call stores exactly the entries this call counted.
+ *   spg_csr_binop: takes the workspace exactly as spg_csr_binop_nnz left it, for the same op, A
+ *     and B; C->indptr is the array that call wrote, C->indices / C->values hold C->nnz = nnzC
+ *     entries.  Stream-ordered; does not wait.
+ *   Neither call allocates device memory: every device scalar lives in the workspace.
+ *   Status: NULL handle SPG_STATUS_NOT_INITIALIZED (checked first).  SPG_STATUS_INVALID_VALUE
+ *     for an op that is none of the three; a NULL A, B, workspace_bytes or nnzC; a NULL C_indptr
+ *     with a workspace; a shape, value-type or indptr-type mismatch between A and B; a
+ *     C_indptr_type that is neither index type; a workspace below the queried size
+ *     (spg_csr_binop: or NULL); a NULL C; a C that is not A's shape and value type; a NULL array
+ *     that is needed.
+ *   Degenerate sizes: rows == 0 succeeds without a launch; nnz(A) == 0 and nnz(B) == 0 are valid
+ *     and still evaluate the other operand against 0 (0 * inf = NaN is stored).
+ *   Aliasing: the inputs are only read, so A and B may be the same arrays; a C array overlapping
+ *     an input is undefined.
+ *   Timing: the mark and count kernels (k_bo_mark, k_bo_count) under SPG_PHASE_SYMBOLIC, the
+ *     three scans under SPG_PHASE_SCAN, the value kernel (k_bo_fill) under SPG_PHASE_NUMERIC. */
+typedef enum { SPG_BINOP_MUL = 0, SPG_BINOP_MAX = 1, SPG_BINOP_MIN = 2 } spg_binop_t;
+
+spg_status_t spg_csr_binop_nnz(spg_handle_t handle, spg_binop_t op, const spg_csr_t *A,
+                               const spg_csr_t *B, void *C_indptr, spg_index_t C_indptr_type,
+                               int64_t *nnzC, size_t *workspace_bytes, void *workspace);
+spg_status_t spg_csr_binop(spg_handle_t handle, spg_binop_t op, const spg_csr_t *A,
+                           const spg_csr_t *B, spg_csr_t *C, size_t workspace_bytes,
+                           void *workspace);
+
+/* Sparse times dense, element-wise: out_values[e] = A.values[e] * D(i, j) for every stored entry
+ * e = (i, j) of A -- scipy's A.multiply(dense), which keeps every stored entry, products that are
+ * 0 or -0.0 included: the structure is A's and only values are written.  (cupyx's
+ * multiply_by_dense, cupy-src/cupyx/scipy/sparse/_csr.py:617-718, reached from multiply at
+ * :328-342.  Added within 0.2.0: a caller detects it by symbol lookup.)
+ *   D: D->rows is A->rows or 1, D->cols is A->cols or 1; an axis of extent 1 is broadcast (its
+ *     index reads element 0): a full matrix, a row vector (column scaling), a column vector (row
+ *     scaling) or 1 x 1.  Either order, any ld at least the minor extent, A's value type.
+ *   The product is SPG_BINOP_MUL's: rounded once, complex (ac - bd) + (ad + bc)i part by part.
+ *   A need not be canonical (the operation is per stored entry, as in scipy); both indptr types.
+ *     Indices must lie in [0, cols) (not checked).
+ *   out_values == A->values exactly (an in-place scale) is allowed; any other overlap is undefined.
+ *   No workspace.  Stream-ordered; does not wait.  nnz == 0 and rows == 0 succeed without a
+ *   launch.  Timed under SPG_PHASE_NUMERIC (k_bo_mul_dense, one launch).
+ *   Status: spg_spmm's rule -- NULL handle SPG_STATUS_NOT_INITIALIZED (checked first);
+ *   SPG_STATUS_INVALID_VALUE for a NULL A or D, a NULL array that is needed, a value type other
+ *   than A's, an order that is neither, an ld below the minor extent -- and INVALID_VALUE for a D
+ *   extent that is neither A's nor 1. */
+spg_status_t spg_csr_mul_dense(spg_handle_t handle, const spg_csr_t *A, const spg_dense_t *D,
+                               void *out_values);
+
 /* Canonicalisation: C = A with its entries grouped by row, sorted, its duplicates summed and / or
  * its zeros dropped, from CSR or COO input, in two calls like the addition -- a structure pass that
  * writes C's row pointer and returns nnz(C), then a value pass into the caller's C.
@@ -600,12 +680,14 @@ typedef enum {
     SPG_PHASE_SYMBOLIC = 2,   /* k_row (count) / k_tile_sym(_seg) / k_symbolic;    */
                               /* spg_csrgeam_nnz's k_geam_mark / k_geam_count;     */
                               /* spg_dense2csr_nnz's k_dn_count / k_dn_indptr;     */
-                              /* spg_csr_extract_nnz's k_ex_mark / k_ex_count      */
+                              /* spg_csr_extract_nnz's k_ex_mark / k_ex_count;     */
+                              /* spg_csr_binop_nnz's k_bo_mark / k_bo_count        */
     SPG_PHASE_NUMERIC = 3,    /* k_row / k_tile_dn / k_tile_sp / k_tile /          */
                               /* k_numeric: values (ALG1 also structure); one       */
                               /* kernel per launch; spg_csrgeam's k_geam_fill;      */
                               /* spg_dense2csr's k_dn_fill; spg_csr_extract's       */
-                              /* k_ex_fill                                          */
+                              /* k_ex_fill; spg_csr_binop's k_bo_fill;              */
+                              /* spg_csr_mul_dense's k_bo_mul_dense                 */
     SPG_PHASE_COMPACT = 4,    /* k_compact: ALG1 copy into C                        */
     SPG_PHASE_VALIDATE = 5,   /* k_validate                                         */
     SPG_PHASE_SPILL = 6,      /* k_symbolic / k_numeric over the rows the short-row */

@@ -30,6 +30,7 @@ SPG_C_64F = 5
 SPG_ALG_DEFAULT, SPG_ALG1, SPG_ALG2, SPG_ALG3 = 0, 1, 2, 3
 SPG_ORDER_COL, SPG_ORDER_ROW = 1, 2
 SPG_CANON_SORT, SPG_CANON_SUM, SPG_CANON_DROP_ZEROS = 1, 2, 4
+SPG_BINOP_MUL, SPG_BINOP_MAX, SPG_BINOP_MIN = 0, 1, 2
 
 STATUS_NAMES = {
     0: "SPG_STATUS_SUCCESS", 1: "SPG_STATUS_NOT_INITIALIZED", 2: "SPG_STATUS_ALLOC_FAILED",
@@ -50,7 +51,8 @@ EXPORTS = ("spg_version", "spg_build_info", "spg_status_string", "spg_create", "
            "spg_spgemm_ws", "spg_plan_info", "spg_tile_value_offsets", "spg_tile_values",
            "spg_numeric_tiles", "spg_cols16_split", "spg_cols16_join", "spg_spmm", "spg_csr2csc",
            "spg_csrgeam_nnz", "spg_csrgeam", "spg_canonicalize_nnz", "spg_canonicalize",
-           "spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr", "spg_csr_extract_nnz", "spg_csr_extract")
+           "spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr", "spg_csr_extract_nnz", "spg_csr_extract",
+           "spg_csr_binop_nnz", "spg_csr_binop", "spg_csr_mul_dense")
 
 # the entry points of the format operations, added within 0.2.0: an older development build
 # (SPG_LIB) may lack them, and the containers then keep their torch form (exports)
@@ -59,6 +61,7 @@ CSRGEAM = ("spg_csrgeam_nnz", "spg_csrgeam")
 CANONICALIZE = ("spg_canonicalize_nnz", "spg_canonicalize")
 EXTRACT = ("spg_csr_extract_nnz", "spg_csr_extract")
 DENSE_CONVERT = ("spg_csr2dense", "spg_dense2csr_nnz", "spg_dense2csr")
+ELEMENTWISE = ("spg_csr_binop_nnz", "spg_csr_binop", "spg_csr_mul_dense")
 
 PHASES = ("products", "scan", "symbolic", "numeric", "compact", "validate", "spill", "spmv", "b_layout")
 NUM_PHASES = 9
@@ -150,6 +153,10 @@ def load():
             "spg_csr_extract_nnz": (ctypes.c_int, [vp, csrp, selp, selp, vp, ctypes.c_int, ctypes.POINTER(i64),
                                                    ctypes.POINTER(sz), vp]),
             "spg_csr_extract": (ctypes.c_int, [vp, csrp, selp, selp, csrp, sz, vp]),
+            "spg_csr_binop_nnz": (ctypes.c_int, [vp, ctypes.c_int, csrp, csrp, vp, ctypes.c_int, ctypes.POINTER(i64),
+                                                 ctypes.POINTER(sz), vp]),
+            "spg_csr_binop": (ctypes.c_int, [vp, ctypes.c_int, csrp, csrp, csrp, sz, vp]),
+            "spg_csr_mul_dense": (ctypes.c_int, [vp, csrp, dnp, vp]),
             "spg_csr2dense": (ctypes.c_int, [vp, csrp, dnp]),
             "spg_dense2csr_nnz": (ctypes.c_int, [vp, dnp, vp, ctypes.c_int, ctypes.POINTER(i64),
                                                  ctypes.POINTER(sz), vp]),

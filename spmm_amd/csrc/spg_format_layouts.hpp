@@ -1,5 +1,5 @@
 // spg_format_layouts.hpp -- the workspace carves of the format operations (spg_csr2csc,
-// spg_csrgeam, spg_dense2csr, spg_canonicalize, spg_csr_extract): where every region of a caller's
+// spg_csrgeam, spg_csr_binop, spg_dense2csr, spg_canonicalize, spg_csr_extract): where every region of a caller's
 // workspace lies and how many bytes the size query answers.  Pure host arithmetic over the
 // operands' shapes: no HIP, so tests/hip/format_layouts_check.cpp builds it with a plain C++17
 // compiler and tests/test_format_layouts_cpu.py pins every answer without a device.
@@ -115,6 +115,35 @@ inline GmLayout gm_layout(const spg_csr_t& A, const spg_csr_t& B) {
     L.status_b = c.take(status_bytes(B.nnz));
     L.status_r = c.take(status_bytes(A.rows));
     L.S = c.take(ips * ((size_t)B.nnz + 1));
+    L.cnt = c.take(sizeof(int64_t) * ((size_t)A.rows + 1));
+    L.total = c.total();
+    return L;
+}
+
+// Workspace carve of spg_csr_binop_nnz / spg_csr_binop (offsets from the 256-byte aligned base).
+// SA and SB stay for the value call.
+struct BoLayout {
+    int64_t chunksA = 0, chunksB = 0;   // wave chunks of GM_CHUNK entries
+    size_t scalars = 0;                 // 16 int64: [0] a scan's total, [1] its overflow flag
+    size_t status_a = 0, status_b = 0, status_r = 0;   // look-back words of the scans over A's entries / B's / the rows
+    size_t SA = 0;                      // nnz(A) + 1 IP: A's kept marks, scanned in place
+    size_t SB = 0;                      // nnz(B) + 1 IP: the kept B-only marks, scanned in place
+    size_t cnt = 0;                     // rows + 1 int64: entries per row of C
+    size_t total = 0;                   // bytes to ask for (256 of slack for the base alignment)
+};
+
+inline BoLayout bo_layout(const spg_csr_t& A, const spg_csr_t& B) {
+    BoLayout L;
+    const size_t ips = index_bytes(A.indptr_type);
+    L.chunksA = (A.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    L.chunksB = (B.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    Carver c;
+    L.scalars = c.scalars();
+    L.status_a = c.take(status_bytes(A.nnz));
+    L.status_b = c.take(status_bytes(B.nnz));
+    L.status_r = c.take(status_bytes(A.rows));
+    L.SA = c.take(ips * ((size_t)A.nnz + 1));
+    L.SB = c.take(ips * ((size_t)B.nnz + 1));
     L.cnt = c.take(sizeof(int64_t) * ((size_t)A.rows + 1));
     L.total = c.total();
     return L;

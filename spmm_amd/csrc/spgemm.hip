@@ -27,6 +27,7 @@
 #include "spgemm_spmm.hpp"
 #include "spgemm_transpose.hpp"
 #include "spgemm_geam.hpp"
+#include "spgemm_binop.hpp"
 #include "spgemm_canon.hpp"
 #include "spgemm_extract.hpp"
 #include "spgemm_dense.hpp"
@@ -1820,6 +1821,63 @@ spg_status_t gm_values(spg_handle_t h, const spg_csr_t& A, const spg_csr_t& B, s
     return SPG_STATUS_SUCCESS;
 }
 
+// ----------------------------------------------------------------------------- spg_csr_binop / spg_csr_mul_dense
+
+inline spg_status_t bo_check_op(spg_binop_t op) {
+    return op == SPG_BINOP_MUL || op == SPG_BINOP_MAX || op == SPG_BINOP_MIN ? SPG_STATUS_SUCCESS
+                                                                             : SPG_STATUS_INVALID_VALUE;
+}
+
+template <typename IP, typename CP, typename T>
+spg_status_t bo_structure(spg_handle_t h, int op, const spg_csr_t& A, const spg_csr_t& B, const BoLayout& L,
+                          char* ws, CP* Cp, int64_t* nnzC) {
+    int64_t* scal = (int64_t*)(ws + L.scalars);
+    IP* SA = (IP*)(ws + L.SA);
+    IP* SB = (IP*)(ws + L.SB);
+    int64_t* cnt = (int64_t*)(ws + L.cnt);
+    spg_status_t st = SPG_STATUS_SUCCESS;
+    if (A.nnz + B.nnz > 0) {
+        timed_launch(h, SPG_PHASE_SYMBOLIC, k_bo_mark<IP, T>,
+                     dim3((unsigned)grid_for(L.chunksA + L.chunksB, GM_WPB)), dim3(GM_WPB * WAVE), op, A.rows, A.nnz,
+                     L.chunksA, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices,
+                     (const T*)A.values, (const IP*)B.indptr, (const int32_t*)B.indices, (const T*)B.values, SA, SB);
+        SPG_LAUNCHED(h);
+    }
+    if ((st = launch_scan<IP, IP>(h, A.nnz, SA, SA, (unsigned long long*)(ws + L.status_a), scal, true))) return st;
+    if ((st = launch_scan<IP, IP>(h, B.nnz, SB, SB, (unsigned long long*)(ws + L.status_b), scal, true))) return st;
+    timed_launch(h, SPG_PHASE_SYMBOLIC, k_bo_count<IP>, dim3(strided_grid(A.rows, 256)), dim3(256), A.rows,
+                 (const IP*)A.indptr, (const IP*)B.indptr, (const IP*)SA, (const IP*)SB, cnt);
+    SPG_LAUNCHED(h);
+    if ((st = launch_scan<CP, int64_t>(h, A.rows, cnt, Cp, (unsigned long long*)(ws + L.status_r), scal, true)))
+        return st;
+    return scan_total(h, scal, nnzC);
+}
+
+template <typename IP, typename CP, typename T>
+spg_status_t bo_values(spg_handle_t h, int op, const spg_csr_t& A, const spg_csr_t& B, spg_csr_t& C,
+                       const BoLayout& L, char* ws) {
+    timed_launch(h, SPG_PHASE_NUMERIC, k_bo_fill<IP, CP, T>,
+                 dim3((unsigned)grid_for(L.chunksA + L.chunksB, GM_WPB)), dim3(GM_WPB * WAVE), op, A.rows, A.nnz,
+                 L.chunksA, B.nnz, L.chunksB, (const IP*)A.indptr, (const int32_t*)A.indices, (const T*)A.values,
+                 (const IP*)B.indptr, (const int32_t*)B.indices, (const T*)B.values, (const IP*)(ws + L.SA),
+                 (const IP*)(ws + L.SB), (const CP*)C.indptr, (int32_t*)C.indices, (T*)C.values);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
+template <typename IP, typename T>
+spg_status_t bo_mul_dense(spg_handle_t h, const spg_csr_t& A, const spg_dense_t& D, void* out) {
+    const bool row = D.order == SPG_ORDER_ROW;
+    // elements between consecutive rows / columns of D; 0 along a broadcast axis
+    const int64_t sr = D.rows == 1 ? 0 : row ? D.ld : 1, sc = D.cols == 1 ? 0 : row ? 1 : D.ld;
+    const int64_t chunks = (A.nnz + GM_CHUNK - 1) / GM_CHUNK;
+    timed_launch(h, SPG_PHASE_NUMERIC, k_bo_mul_dense<IP, T>, dim3((unsigned)grid_for(chunks, GM_WPB)),
+                 dim3(GM_WPB * WAVE), A.rows, A.nnz, chunks, (const IP*)A.indptr, (const int32_t*)A.indices,
+                 (const T*)A.values, (const T*)D.values, sr, sc, (T*)out);
+    SPG_LAUNCHED(h);
+    return SPG_STATUS_SUCCESS;
+}
+
 // ----------------------------------------------------------------------------- spg_csr2dense / spg_dense2csr
 
 // what the three entry points ask of a dense operand (check_dense, plus a known value type and
@@ -2558,6 +2616,64 @@ spg_status_t spg_csrgeam(spg_handle_t h, const void* alpha, const spg_csr_t* A, 
         std::memcpy(&be, beta, sizeof(T));
         return dispatch_index(A->indptr_type, C->indptr_type, [&](auto ip, auto cp) {
             return gm_values<decltype(ip), decltype(cp), T>(h, *A, *B, *C, L, ws_base(workspace), al, be);
+        });
+    });
+}
+
+spg_status_t spg_csr_binop_nnz(spg_handle_t h, spg_binop_t op, const spg_csr_t* A, const spg_csr_t* B,
+                               void* C_indptr, spg_index_t C_indptr_type, int64_t* nnzC, size_t* workspace_bytes,
+                               void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!workspace_bytes || !nnzC) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = gm_check(A, B);
+    if (st || (st = bo_check_op(op)) || (st = check_index_type(C_indptr_type))) return st;
+    const BoLayout L = bo_layout(*A, *B);
+    if (size_query(L.total, workspace_bytes, workspace, st)) return st;   // (host arithmetic only)
+    if (!C_indptr) return SPG_STATUS_INVALID_VALUE;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    if (A->rows == 0) return empty_structure(h, C_indptr, C_indptr_type, 1, nnzC);   // an empty row pointer's one entry
+    return dispatch_value(A->value_type, [&](auto tag) {
+        return dispatch_index(A->indptr_type, C_indptr_type, [&](auto ip, auto cp) {
+            using CP = decltype(cp);
+            return bo_structure<decltype(ip), CP, decltype(tag)>(h, (int)op, *A, *B, L, ws_base(workspace),
+                                                                 (CP*)C_indptr, nnzC);
+        });
+    });
+}
+
+spg_status_t spg_csr_binop(spg_handle_t h, spg_binop_t op, const spg_csr_t* A, const spg_csr_t* B, spg_csr_t* C,
+                           size_t workspace_bytes, void* workspace) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    if (!C || !workspace) return SPG_STATUS_INVALID_VALUE;
+    spg_status_t st = gm_check(A, B);
+    if (st || (st = bo_check_op(op))) return st;
+    const BoLayout L = bo_layout(*A, *B);
+    if ((st = check_result(C, A->rows, A->cols, A->value_type, workspace_bytes, L.total))) return st;
+    if (A->rows == 0 || C->nnz == 0 || A->nnz + B->nnz == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    return dispatch_value(A->value_type, [&](auto tag) {
+        return dispatch_index(A->indptr_type, C->indptr_type, [&](auto ip, auto cp) {
+            return bo_values<decltype(ip), decltype(cp), decltype(tag)>(h, (int)op, *A, *B, *C, L,
+                                                                        ws_base(workspace));
+        });
+    });
+}
+
+spg_status_t spg_csr_mul_dense(spg_handle_t h, const spg_csr_t* A, const spg_dense_t* D, void* out_values) {
+    if (!h) return SPG_STATUS_NOT_INITIALIZED;
+    spg_status_t st = check_csr(A);
+    if (st || (st = check_dense(D))) return st;
+    if (D->value_type != A->value_type) return SPG_STATUS_INVALID_VALUE;
+    if ((D->rows != A->rows && D->rows != 1) || (D->cols != A->cols && D->cols != 1)) return SPG_STATUS_INVALID_VALUE;
+    if (A->nnz > 0 && !out_values) return SPG_STATUS_INVALID_VALUE;
+    if (A->rows == 0 || A->nnz == 0) return SPG_STATUS_SUCCESS;
+    DeviceGuard dg_(h->device);
+    SPG_HIP(h, dg_.err);
+    return dispatch_value(A->value_type, [&](auto tag) {
+        return dispatch_index(A->indptr_type, [&](auto ip) {
+            return bo_mul_dense<decltype(ip), decltype(tag)>(h, *A, *D, out_values);
         });
     });
 }

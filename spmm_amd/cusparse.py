@@ -728,6 +728,128 @@ def csrgeam2(a, b, alpha=1, beta=1):
 csrgeam = csrgeam2
 
 
+def has_elementwise() -> bool:
+    return _lib.exports(*_lib.ELEMENTWISE)
+
+
+_BINOPS = {"multiply": _lib.SPG_BINOP_MUL, "maximum": _lib.SPG_BINOP_MAX, "minimum": _lib.SPG_BINOP_MIN}
+
+
+def _binop_arrays(ax, aj, ap, bx, bj, bp, shape, op: int):
+    """(data, indices, indptr) of op(A, B) (an SPG_BINOP_* code) for the CSR arrays of two canonical
+    matrices of one shape and value type, on spg_csr_binop_nnz + spg_csr_binop.  The operands' row
+    pointers are int32 whenever both entry counts fit; C's is tried as int32 first and as int64
+    after an OVERFLOW answer."""
+    dev, dt = ax.device, ax.dtype
+    m, n = shape
+    na, nb = int(ax.numel()), int(bx.numel())
+    ipd = _indptr_dtype(max(na, nb))
+    h = _handle_on(dev)
+    ap, bp = ap.to(ipd).contiguous(), bp.to(ipd).contiguous()
+    aj, ax, bj, bx = aj.contiguous(), ax.contiguous(), bj.contiguous(), bx.contiguous()
+    va, vb = ctypes.byref(_view(m, n, na, ap, aj, ax, dt)), ctypes.byref(_view(m, n, nb, bp, bj, bx, dt))
+    tries = (torch.int32, torch.int64) if ipd is torch.int32 else (torch.int64,)
+    # _two_phase's steps, with one branch it has not: C's structure depends on the values, so
+    # nnz(C) == 0 is an ordinary answer here, and then there is nothing for a value call to write
+    structure = functools.partial(h.lib.spg_csr_binop_nnz, h.ptr, op, va, vb)
+    nnz = ctypes.c_int64(0)
+    nnz_p = ctypes.byref(nnz)
+    ws, ws_bytes, wp = _sized_workspace(lambda wb, p: structure(None, _IT[tries[0]], nnz_p, wb, p),
+                                        "spg_csr_binop_nnz", dev)
+    wb = ctypes.byref(ws_bytes)
+    st, indptr = _structure(lambda ip, it: structure(ip, it, nnz_p, wb, wp), m, tries, dev)
+    check(st, "spg_csr_binop_nnz")
+    data, indices, vc = _empty_c(m, n, int(nnz.value), indptr, dt, dev)
+    if nnz.value:
+        check(h.lib.spg_csr_binop(h.ptr, op, va, vb, ctypes.byref(vc), ws_bytes, wp), "spg_csr_binop")
+    return data, indices, indptr
+
+
+def csrbinop(a, b, op):
+    """Element-wise ``op(A, B)`` of two CSR matrices, ``op`` one of ``"multiply"``, ``"maximum"``,
+    ``"minimum"`` -- what cupyx's ``csr_matrix.multiply`` / ``maximum`` / ``minimum`` compute with
+    kernels of their own (modify_src/cupy-src/cupyx/scipy/sparse/_csr.py:328-342, :297-326), on
+    ``spg_csr_binop_nnz`` + ``spg_csr_binop``.
+
+    Args:
+        a (csr_matrix): sparse matrix A, canonical format.
+        b (csr_matrix): sparse matrix B, canonical format, A's shape.
+        op (str): the operation's name.
+
+    Returns:
+        csr_matrix: C, canonical: over the union of the two patterns the entries whose result is
+        not zero, array for array what scipy's ``A.multiply(B)`` / ``A.maximum(B)`` /
+        ``A.minimum(B)`` gives.
+    """
+    if not (check_availability("csrgeam2") and has_elementwise()):   # a device, and a library with the entry points
+        raise RuntimeError("csrbinop is not available.")
+    _check_type(a, csr_matrix)
+    _check_type(b, csr_matrix)
+    if op not in _BINOPS:
+        raise ValueError(f"op must be one of {', '.join(_BINOPS)} (actual: {op!r})")
+    assert a.has_canonical_format
+    assert b.has_canonical_format
+    if a.shape != b.shape:
+        raise ValueError("inconsistent shapes")
+    if a.device.type != "cuda" or b.device != a.device:
+        raise RuntimeError("csrbinop needs device-resident operands on one device")
+    a, b = _cast_common_type(a, b)
+    parts = _binop_arrays(a.data, a.indices, a.indptr, b.data, b.indices, b.indptr, a.shape, _BINOPS[op])
+    return csr_matrix._from_parts(*parts, a.shape, canonical=True)
+
+
+def _mul_dense_arrays(data, indices, indptr, shape, d: torch.Tensor, out=None):
+    """data[e] * d[i, j] for every stored entry e = (i, j) of the m x n CSR arrays, on
+    spg_csr_mul_dense: a new tensor, or ``out`` (which may be ``data`` itself).  ``d`` is a 2-D
+    tensor of data's dtype on its device, m or 1 rows by n or 1 columns (an extent of 1 is
+    broadcast), addressed in place when it has unit stride along its rows or its columns and
+    copied row-major otherwise."""
+    dev, dt = data.device, data.dtype
+    m, n = shape
+    nnz = int(data.numel())
+    if d.ndim != 2 or d.shape[0] not in (m, 1) or d.shape[1] not in (n, 1):
+        raise ValueError("inconsistent shapes")
+    if d.dtype != dt or d.device != dev:
+        raise TypeError("d must be a tensor of the matrix's type on its device")
+    if out is None:
+        out = torch.empty(nnz, dtype=dt, device=dev)
+    if nnz == 0:
+        return out
+    layout = _dense_layout(d)
+    if layout is None:
+        d = _in_order(d, _lib.SPG_ORDER_ROW)
+        layout = _dense_layout(d)
+    data, indices, indptr = data.contiguous(), indices.contiguous(), indptr.contiguous()
+    h = _handle_on(dev)
+    va = _view(m, n, nnz, indptr, indices, data, dt)
+    vd = _dense_view(d, *layout)
+    check(h.lib.spg_csr_mul_dense(h.ptr, ctypes.byref(va), ctypes.byref(vd), ctypes.c_void_p(out.data_ptr())),
+          "spg_csr_mul_dense")
+    return out
+
+
+def multiply_by_dense(a, d):
+    """Element-wise ``A.multiply(d)`` for a CSR matrix and a dense operand that broadcasts to its
+    shape -- cupyx's ``multiply_by_dense`` (modify_src/cupy-src/cupyx/scipy/sparse/_csr.py:617-718),
+    on ``spg_csr_mul_dense``.  ``d`` is a 2-D tensor (or numpy array, uploaded) of shape (m, n),
+    (1, n), (m, 1) or (1, 1).  Every stored entry is kept, products that are zero included: the
+    result is a csr_matrix on copies of A's structure, which need not be canonical."""
+    if not (check_availability("csrgeam2") and has_elementwise()):   # a device, and a library with the entry points
+        raise RuntimeError("multiply_by_dense is not available.")
+    _check_type(a, csr_matrix)
+    if not isinstance(d, (torch.Tensor, np.ndarray)):
+        raise TypeError("unsupported type (actual: {})".format(type(d)))
+    if not isinstance(d, torch.Tensor):
+        d = torch.from_numpy(np.asarray(d))
+    if d.ndim != 2 or d.shape[0] not in (a.shape[0], 1) or d.shape[1] not in (a.shape[1], 1):
+        raise ValueError("inconsistent shapes")
+    _check_device(a, "multiply_by_dense")
+    a = _promoted("multiply_by_dense", a, d.dtype)
+    d = d.to(device=a.device, dtype=a.data.dtype)
+    data = _mul_dense_arrays(a.data, a.indices, a.indptr, a.shape, d)
+    return csr_matrix._from_parts(data, a.indices.clone(), a.indptr.clone(), a.shape, canonical=a._canonical)
+
+
 def _canonicalize_arrays(data, indices, indptr, coo_rows, shape, ops: int, indptr_dtype=None):
     """(data, indices, indptr) of the m x n matrix after ``ops`` (a sum of the SPG_CANON_* bits),
     on spg_canonicalize_nnz + spg_canonicalize.  The input is CSR (``coo_rows`` None) or COO

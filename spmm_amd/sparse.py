@@ -207,6 +207,93 @@ def _geam_torch(a: "csr_matrix", b: "csr_matrix", alpha, beta) -> "csr_matrix":
                                   _indptr_from_rows(rows, m, ipd), (m, n), canonical=True)
 
 
+def _mul_rn(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """x * y element by element with every product and sum rounded on its own: a complex product
+    is (ac - bd) + (ad + bc)i on the real parts (torch's own complex multiply may fuse them)."""
+    if not x.is_complex():
+        return x * y
+    xr, yr = torch.view_as_real(x), torch.view_as_real(y)
+    a, b, c, d = xr[..., 0], xr[..., 1], yr[..., 0], yr[..., 1]
+    return torch.view_as_complex(torch.stack((a * c - b * d, a * d + b * c), dim=-1).contiguous())
+
+
+def _nonzero_bits(x: torch.Tensor) -> torch.Tensor:
+    """x != 0 decided on the integer bits (spg_dense2csr's test): +-0 false; denormals, +-inf and
+    NaN true; a complex value false only when both parts are +-0."""
+    parts = torch.view_as_real(x) if x.is_complex() else x
+    bits = parts.contiguous().view(torch.int32 if parts.dtype == torch.float32 else torch.int64)
+    keep = (bits & (0x7FFFFFFF if parts.dtype == torch.float32 else 0x7FFFFFFFFFFFFFFF)) != 0
+    return keep.any(dim=-1) if x.is_complex() else keep
+
+
+def _less(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """x < y; for complex values scipy's lexicographic order, re first."""
+    if not x.is_complex():
+        return x < y
+    xr, yr = torch.view_as_real(x), torch.view_as_real(y)
+    return torch.where(xr[..., 0] == yr[..., 0], xr[..., 1] < yr[..., 1], xr[..., 0] < yr[..., 0])
+
+
+def _select(take_y: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """take_y ? y : x, the chosen operand moved bit for bit."""
+    if not x.is_complex():
+        return torch.where(take_y, y, x)
+    return torch.view_as_complex(torch.where(take_y[..., None], torch.view_as_real(y), torch.view_as_real(x)).contiguous())
+
+
+_BINOP_NAMES = ("multiply", "maximum", "minimum")
+
+
+def _binop_torch(a: "csr_matrix", b: "csr_matrix", op: str) -> "csr_matrix":
+    """op(A, B) of two canonical CSR matrices as torch ops -- spg_csr_binop's rule
+    (include/spgemm.h): over the union of the two patterns r = op(a, b), an operand without the
+    entry contributing +0; the entries with r != 0 (on the bits) are kept.  multiply: a * b;
+    maximum: a < b ? b : a; minimum: b < a ? b : a."""
+    if op not in _BINOP_NAMES:
+        raise ValueError(f"op must be one of {', '.join(_BINOP_NAMES)} (actual: {op!r})")
+    if a.shape != b.shape:
+        raise ValueError("inconsistent shapes")
+    m, n = a.shape
+    dt = _TORCH_OF[np.dtype(np.promote_types(a.dtype, b.dtype))]
+    ka = a._row_ids() * max(n, 1) + a.indices.to(torch.int64)
+    kb = b._row_ids() * max(n, 1) + b.indices.to(torch.int64)
+    keys = torch.unique(torch.cat((ka, kb)))   # sorted: row-major, columns ascending
+    a_at = torch.zeros(keys.numel(), dtype=dt, device=a.device)
+    b_at = torch.zeros(keys.numel(), dtype=dt, device=a.device)
+    a_at[torch.searchsorted(keys, ka)] = a.data.to(dt)
+    b_at[torch.searchsorted(keys, kb)] = b.data.to(dt)
+    if op == "multiply":
+        r = _mul_rn(a_at, b_at)
+    elif op == "maximum":
+        r = _select(_less(a_at, b_at), a_at, b_at)
+    else:
+        r = _select(_less(b_at, a_at), a_at, b_at)
+    keep = _nonzero_bits(r)
+    keys, r = keys[keep], r[keep].contiguous()
+    rows = torch.div(keys, max(n, 1), rounding_mode="floor")
+    ipd = _indptr_dtype(keys.numel())
+    return csr_matrix._from_parts(r, (keys - rows * max(n, 1)).to(torch.int32),
+                                  _indptr_from_rows(rows, m, ipd), (m, n), canonical=True)
+
+
+def _mul_dense_torch(data, indices, indptr, n_major: int, d: torch.Tensor) -> torch.Tensor:
+    """data[e] * d[i, j] for every stored entry e = (i, j) of compressed arrays as torch ops --
+    spg_csr_mul_dense's rule: d has n_major or 1 rows and n_minor or 1 columns, an extent of 1 is
+    broadcast."""
+    counts = (indptr[1:] - indptr[:-1]).to(torch.int64)
+    major = torch.repeat_interleave(torch.arange(n_major, device=data.device), counts)
+    minor = indices.to(torch.int64)
+    i = major if d.shape[0] > 1 else torch.zeros_like(major)
+    j = minor if d.shape[1] > 1 else torch.zeros_like(minor)
+    return _mul_rn(data, d[i, j])
+
+
+def _is_scalar(x) -> bool:
+    """A Python or numpy number, or a 0-d array or tensor."""
+    return isinstance(x, (int, float, complex, np.number, np.bool_)) or (
+        isinstance(x, (torch.Tensor, np.ndarray)) and x.ndim == 0)
+
+
 def _is_int(x) -> bool:
     return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
 
@@ -343,6 +430,35 @@ class _SparseBase:
     def __neg__(self):
         return -self.tocsr()
 
+    # ------------------------------------------------------------------ element-wise operations
+    # (cupyx _base.py: every format multiplies, and takes maximum / minimum, through its CSR form)
+    def multiply(self, other):
+        return self.tocsr().multiply(other)
+
+    def maximum(self, other):
+        return self.tocsr().maximum(other)
+
+    def minimum(self, other):
+        return self.tocsr().minimum(other)
+
+    def __mul__(self, other):
+        return self.tocsr()._scale(other) if _is_scalar(other) else NotImplemented
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, other):
+        raise NotImplementedError("division of a sparse matrix is not supported")
+
+    __rtruediv__ = __truediv__
+
+    def _compare(self, other):
+        if isspmatrix(other) or _is_dense(other) or _is_scalar(other):
+            raise NotImplementedError("comparison of sparse matrices is not supported")
+        return NotImplemented
+
+    __eq__ = __ne__ = __lt__ = __le__ = __gt__ = __ge__ = _compare
+    __hash__ = object.__hash__
+
     @property
     def shape(self):
         return self._shape
@@ -412,6 +528,93 @@ class _Compressed(_SparseBase):
         out = self.copy()
         out.data = _negated(self.data)
         return out
+
+    # ------------------------------------------------------------------ element-wise operations
+    def _binop_sparse(self, other, op: str):
+        raise NotImplementedError
+
+    def _with_data(self, data):
+        """A matrix of this format with ``data`` on copies of this structure, the canonical flag kept."""
+        arrays = (data, self.indices.clone(), self.indptr.clone())
+        if self.format == "csr":
+            return csr_matrix._from_parts(*arrays, self._shape, canonical=self._canonical)
+        return csc_matrix(arrays, shape=self._shape, canonical=self._canonical)
+
+    def _scale(self, s):
+        """self * s for a scalar (cupyx _data.py _mul_scalar): the structure copied, every value
+        multiplied, in the common type of the matrix and the scalar."""
+        s = s.item() if isinstance(s, (torch.Tensor, np.ndarray)) else s
+        dt = np.result_type(self.dtype, s)
+        if np.dtype(dt) not in _TORCH_OF or _TORCH_OF[np.dtype(dt)] not in _VALUE_TYPES:
+            raise TypeError(f"unsupported dtype {dt}")
+        data = self.data.to(_TORCH_OF[np.dtype(dt)])
+        scaled = _scaled(s, data)
+        return self._with_data(scaled.clone() if scaled is data else scaled)
+
+    def _mul_dense(self, d):
+        """self.multiply(d) for a dense vector or matrix that broadcasts to this shape."""
+        m, n = self._shape
+        if isinstance(d, np.ndarray):
+            d = torch.from_numpy(d if d.flags.writeable else d.copy())
+        if d.ndim == 1:
+            d = d.reshape(1, -1)   # a 1-D operand is a row vector
+        if d.ndim != 2:
+            raise ValueError("could not interpret dimensions")
+        r, c = int(d.shape[0]), int(d.shape[1])
+        if not all(x == y or x == 1 or y == 1 for x, y in ((r, m), (c, n))):
+            raise ValueError("inconsistent shapes")
+        if r not in (m, 1) or c not in (n, 1):
+            raise NotImplementedError("multiply by a dense operand larger than the sparse matrix "
+                                      "(broadcasting the sparse operand) is not supported")
+        dt = np.promote_types(self.dtype, np.dtype(str(d.dtype).replace("torch.", "")))
+        if np.dtype(dt) not in _TORCH_OF or _TORCH_OF[np.dtype(dt)] not in _VALUE_TYPES:
+            raise TypeError(f"unsupported dtype {dt}")
+        tdt = _TORCH_OF[np.dtype(dt)]
+        data, d = self.data.to(tdt), d.to(device=self.device, dtype=tdt)
+        csr = self.format == "csr"
+        if not csr:   # the CSC arrays are the CSR of the transpose
+            d = d.t()
+        n_major, n_minor = (m, n) if csr else (n, m)
+        if _engine_has(data, _lib.ELEMENTWISE):
+            from . import cusparse
+            return self._with_data(cusparse._mul_dense_arrays(data, self.indices, self.indptr, (n_major, n_minor), d))
+        return self._with_data(_mul_dense_torch(data, self.indices, self.indptr, n_major, d))
+
+    def multiply(self, other):
+        """Point-wise multiplication by a scalar, a dense vector or matrix, or a sparse matrix of
+        this shape (cupyx _csr.py:328-342): scipy's ``multiply``.  A sparse operand gives the
+        canonical matrix of the nonzero products (spg_csr_binop); a dense one, of shape (m, n),
+        (1, n), (m, 1), (1, 1) or (n,), scales every stored entry on a copy of this structure
+        (spg_csr_mul_dense); a scalar scales the data."""
+        if _is_scalar(other):
+            return self._scale(other)
+        if isspmatrix(other):
+            return self._binop_sparse(other, "multiply")
+        if _is_dense(other):
+            return self._mul_dense(other)
+        raise TypeError("expected scalar, dense matrix/vector or csr matrix")
+
+    def _maximum_minimum(self, other, op: str):
+        if _is_scalar(other) or _is_dense(other):
+            raise NotImplementedError(f"{op} with a scalar or a dense operand is not supported")
+        if isspmatrix(other):
+            return self._binop_sparse(other, op)
+        raise TypeError("expected scalar, dense matrix/vector or csr matrix")
+
+    def maximum(self, other):
+        """Element-wise maximum with a sparse matrix of this shape (cupyx _csr.py:297-326): scipy's
+        ``maximum``, the entries that come out zero dropped."""
+        return self._maximum_minimum(other, "maximum")
+
+    def minimum(self, other):
+        """Element-wise minimum with a sparse matrix of this shape: scipy's ``minimum``."""
+        return self._maximum_minimum(other, "minimum")
+
+    def __mul__(self, other):
+        return self._scale(other) if _is_scalar(other) else NotImplemented
+
+    def __rmul__(self, other):
+        return self._scale(other) if _is_scalar(other) else NotImplemented
 
     # ------------------------------------------------------------------ indexing
     def _extract(self, rows_sel, cols_sel):
@@ -650,8 +853,11 @@ class csr_matrix(_Compressed):
     def __mul__(self, other):
         """CSR x sparse: CuPy's _csr.py:151-166 order -- canonicalise both, then spgemm.
         CSR x dense vector (_csr.py:190-216): canonicalise, then spmv.
-        CSR x dense matrix (_csr.py:217-225): canonicalise, then spmm."""
+        CSR x dense matrix (_csr.py:217-225): canonicalise, then spmm.
+        CSR x scalar (_csr.py:153-155): the data scaled."""
         from . import cusparse
+        if _is_scalar(other):
+            return self._scale(other)
         if isinstance(other, (csc_matrix, coo_matrix)):
             other = other.tocsr()
         if isinstance(other, csr_matrix):
@@ -678,6 +884,19 @@ class csr_matrix(_Compressed):
             from . import cusparse
             return cusparse.csrgeam2(self, other, alpha, beta)
         return _geam_torch(self, other, alpha, beta)
+
+    def _binop_sparse(self, other, op: str):
+        """op(self, other) for a sparse operand (cupyx _csr.py:297-342): canonicalise both, then
+        spg_csr_binop for device tensors, else the torch form of the same rule."""
+        self.sum_duplicates()
+        other = other.tocsr()
+        other.sum_duplicates()
+        if other.shape != self.shape:
+            raise NotImplementedError(f"{op} of sparse matrices of different shapes (broadcasting) is not supported")
+        if _engine_has(self.data, _lib.ELEMENTWISE) and other.device == self.device:
+            from . import cusparse
+            return cusparse.csrbinop(self, other, op)
+        return _binop_torch(self, other, op)
 
     def tocsc(self, copy=False) -> "csc_matrix":
         """The same matrix in CSC, array for array what scipy's ``tocsc()`` gives (every
@@ -915,6 +1134,13 @@ class csc_matrix(_Compressed):
         (cupyx _csc.py:250-262)."""
         other = other.tocsc() if isinstance(other, (csr_matrix, csc_matrix)) else other.tocsr().tocsc()
         return self.transpose()._add_sparse(other.transpose(), alpha, beta).transpose()
+
+    def _binop_sparse(self, other, op: str):
+        """op(self, other) as a csc_matrix: a canonical CSC is the canonical CSR of the transpose and
+        the operations commute with transposition, so it is the CSR operation of the two free
+        transposes."""
+        other = other.tocsc() if isinstance(other, (csr_matrix, csc_matrix)) else other.tocsr().tocsc()
+        return self.transpose()._binop_sparse(other.transpose(), op).transpose()
 
     def tocsr(self) -> csr_matrix:
         """The same matrix in CSR: spg_csr2csc for device tensors (a canonical CSC gives a
