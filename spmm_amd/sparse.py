@@ -393,17 +393,39 @@ def _extract_torch(data, indices, indptr, n_major: int, n_minor: int, major_sel,
     return data[e].contiguous(), minor.to(torch.int32), _indptr_from_rows(seg, nr, ipd)
 
 
+def _validate_torch(indptr, indices, nnz: int, n_minor: int) -> int:
+    """spg_validate_csr's verdict (include/spgemm.h) as torch ops, for tensors the engine does not
+    serve: -1 when a segment has a start below 0, an end before its start or an end past ``nnz``,
+    or when an index one of the segments reads is outside [0, n_minor); else 0 when two
+    neighbouring entries of one segment do not ascend strictly; else 1."""
+    ip = indptr.to(torch.int64)
+    p0, p1 = ip[:-1], ip[1:]
+    if p0.numel() == 0:
+        return 1
+    if bool(((p0 < 0) | (p1 < p0) | (p1 > nnz)).any()):
+        return -1
+    first = int(ip[0])   # (well-formed segments follow one another: they read [ip[0], ip[-1]))
+    j = indices[first:int(ip[-1])].to(torch.int64)
+    if j.numel() == 0:
+        return 1
+    if bool(((j < 0) | (j >= n_minor)).any()):
+        return -1
+    seg = torch.repeat_interleave(torch.arange(p0.numel(), device=ip.device), p1 - p0)
+    return 0 if bool(((j[1:] <= j[:-1]) & (seg[1:] == seg[:-1])).any()) else 1
+
+
 def _extract_compressed(data, indices, indptr, n_major: int, n_minor: int, major_sel, minor_sel, canonical):
     """The selected major segments and minor indices of compressed arrays, with the canonical
-    flag of the result: the source's when the minor axis is kept or cut by an ascending range,
-    unknown (``None``: checked lazily) for a list or a descending range."""
+    flag of the result: ``True`` when the source's is and the minor axis is kept or cut by an
+    ascending range, else unknown (``None``: checked lazily) -- a list or a descending range
+    reorders a segment, and any selection may leave out what made the source non-canonical."""
     if _engine_has(data, _lib.EXTRACT, n_minor):
         from . import cusparse
         parts = cusparse._extract_arrays(data, indices, indptr, (n_major, n_minor), major_sel, minor_sel)
     else:
         parts = _extract_torch(data, indices, indptr, n_major, n_minor, major_sel, minor_sel)
     keeps = minor_sel is None or (isinstance(minor_sel, tuple) and minor_sel[1] > 0)
-    return parts, (canonical if keeps else None)
+    return parts, (True if keeps and canonical is True else None)
 
 
 def isspmatrix(x) -> bool:
@@ -752,10 +774,14 @@ class csr_matrix(_Compressed):
     @property
     def has_canonical_format(self) -> bool:
         """indices sorted strictly increasing inside each row (no duplicates).  Evaluated
-        on the device with spg_validate_csr and cached, as CuPy caches it."""
+        on the device with spg_validate_csr and cached, as CuPy caches it; for tensors that are
+        not on a GPU, the torch form of the same rule."""
         if self._canonical is None:
-            from . import cusparse
-            self._canonical = cusparse.validate_csr(self) == 1
+            if _engine_has(self.data, ("spg_validate_csr",), self._shape[1]):
+                from . import cusparse
+                self._canonical = cusparse.validate_csr(self) == 1
+            else:
+                self._canonical = _validate_torch(self.indptr, self.indices, self.nnz, self._shape[1]) == 1
         return self._canonical
 
     @has_canonical_format.setter
@@ -799,24 +825,42 @@ class csr_matrix(_Compressed):
         self._canonical = True
 
     def sort_indices(self) -> None:
-        self.sum_duplicates() if self._canonical is not True else None
+        """Sort the indices of every row in place, stably, duplicates kept (cupyx
+        _compressed.py sort_indices, on csrsort): ``cusparse.csrsort`` for device tensors, else a
+        stable torch sort by (row, column).  A matrix flagged canonical is left alone; any other
+        is sorted afterwards and canonical when it holds no duplicates (the flag: unknown)."""
+        if self._canonical is True:
+            return
+        if _engine_has(self.data, _lib.CANONICALIZE, max(self._shape)):
+            from . import cusparse
+            cusparse.csrsort(self)
+            return
+        key = self._row_ids() * max(self._shape[1], 1) + self.indices.to(torch.int64)
+        _, order = torch.sort(key, stable=True)
+        self.data, self.indices = self.data[order].contiguous(), self.indices[order].contiguous()
+        self._canonical = None
 
     def eliminate_zeros(self) -> None:
         """Drop the stored entries that equal zero, in place, the stored order kept (cupyx
-        _csr.py:288-302): spg_canonicalize for device tensors, else the torch form."""
+        _csr.py:288-302): spg_canonicalize for device tensors, else the torch form.  A canonical
+        matrix stays canonical; one that was not may have lost the twin of its only duplicate, so
+        once an entry is dropped its flag is unknown."""
+        before = self.nnz
         if _engine_has(self.data, _lib.CANONICALIZE, max(self._shape)):
             from . import cusparse
             self.data, self.indices, self.indptr = cusparse._canonicalize_arrays(
                 self.data, self.indices, self.indptr, None, self._shape, _lib.SPG_CANON_DROP_ZEROS,
                 self.indptr.dtype)
-            return
-        keep = self.data != 0
-        if bool(keep.all()):
-            return
-        rows = self._row_ids()[keep]
-        self.data = self.data[keep].contiguous()
-        self.indices = self.indices[keep].contiguous()
-        self.indptr = _indptr_from_rows(rows, self._shape[0], self.indptr.dtype)
+        else:
+            keep = self.data != 0
+            if bool(keep.all()):
+                return
+            rows = self._row_ids()[keep]
+            self.data = self.data[keep].contiguous()
+            self.indices = self.indices[keep].contiguous()
+            self.indptr = _indptr_from_rows(rows, self._shape[0], self.indptr.dtype)
+        if self._canonical is False and self.nnz != before:
+            self._canonical = None
 
     # ------------------------------------------------------------------ conversion
     def astype(self, dtype):
@@ -1092,6 +1136,12 @@ class csc_matrix(_Compressed):
             self.data, self.indices, self.indptr = _dense_to_csr(t.t())
             self._shape = (int(t.shape[0]), int(t.shape[1]))
             self._canonical = True
+            return
+        if isinstance(arg1, _SparseBase):   # a container of this package: its CSC form, the flag carried
+            S = arg1 if isinstance(arg1, csc_matrix) else arg1.tocsr().tocsc()
+            device = torch.device(device) if device is not None else S.device
+            self.data, self.indices, self.indptr = S.data.to(device), S.indices.to(device), S.indptr.to(device)
+            self._shape, self._canonical = S.shape, S._canonical
             return
         if not hasattr(arg1, "tocsc"):
             raise TypeError(f"unsupported csc_matrix argument {type(arg1)}")
